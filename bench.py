@@ -2,6 +2,7 @@
 """bench.py — the driver's measurement contract.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config FILE] [--dtype float32|bfloat16|float16]
+                    [--dump-outputs DIR]
 
 A "step" is one training iteration (forward + backward + gradient all-reduce + SGD update) of
 `e2e_mask_rcnn_R_50_FPN_1x` (BASELINE.json's metric config) on one batch of 2 synthetic
@@ -85,8 +86,28 @@ def parse():
     ap.add_argument("--stub-step", action="store_true",
                     help="test hook: CPU tensors, gloo, a stub step — exercises the launch / world-size / timed-region / "
                          "JSON logic without a GPU; the line is marked as a stub, not a measurement")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write to DIR/<name>.npy (float32, or float64 where the tensor is; rank 0): "
+                         "training = the timed training step run once from the seeded initial state on the last timed "
+                         "batch, its losses and a fixed sample of the updated parameters (see seeded_step_outputs); "
+                         "--eval = every detection field of every image of the last timed step")
     ap.add_argument("opts", nargs=argparse.REMAINDER, default=[])
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def copy_writable(src, dst):
+    """copy the tree under `src` into `dst` with every directory and file writable by this user, whatever the modes of the
+    source (a read-only checkout): MIOpen creates lock files and journals beside its databases and writes new records into
+    them, and fails the first convolution (miopenStatusInternalError) when it cannot"""
+    import shutil
+    for d, _, files in os.walk(src):
+        out = os.path.join(dst, os.path.relpath(d, src))
+        os.makedirs(out, exist_ok=True)
+        for f in files:
+            shutil.copyfile(os.path.join(d, f), os.path.join(out, f))      # contents only: new files take this user's umask
 
 
 def setup_miopen_db(export_dir=None):
@@ -96,7 +117,6 @@ def setup_miopen_db(export_dir=None):
     produced once on an MI355X (`--miopen-search --export-miopen-db DIR`) can be shipped in-tree as
     maskrcnn-benchmark_amd/miopen_db/{db,cache}; it is copied to a scratch dir (MIOpen writes to it)
     and selected through MIOpen's own environment variables.  Must run before `import torch`."""
-    import shutil
     import tempfile
     if export_dir:
         os.makedirs(os.path.join(export_dir, "db"), exist_ok=True)
@@ -104,7 +124,7 @@ def setup_miopen_db(export_dir=None):
         seed = os.path.join(ROOT, "maskrcnn-benchmark_amd", "miopen_db")
         if os.path.isdir(os.path.join(seed, "db")) and not os.listdir(os.path.join(export_dir, "db")):
             # start from the shipped database: only problem keys it does not hold yet are searched
-            shutil.copytree(seed, export_dir, dirs_exist_ok=True)
+            copy_writable(seed, export_dir)
         os.environ["MIOPEN_USER_DB_PATH"] = os.path.join(export_dir, "db")
         os.environ["MIOPEN_CUSTOM_CACHE_DIR"] = os.path.join(export_dir, "cache")
         return "export:" + export_dir
@@ -112,7 +132,7 @@ def setup_miopen_db(export_dir=None):
     if "MIOPEN_USER_DB_PATH" in os.environ or not os.path.isdir(os.path.join(shipped, "db")):
         return None
     scratch = tempfile.mkdtemp(prefix="miopen_db_rank%s_" % os.environ.get("RANK", "0"))
-    shutil.copytree(shipped, scratch, dirs_exist_ok=True)
+    copy_writable(shipped, scratch)
     os.environ["MIOPEN_USER_DB_PATH"] = os.path.join(scratch, "db")
     if os.path.isdir(os.path.join(scratch, "cache")):
         os.environ["MIOPEN_CUSTOM_CACHE_DIR"] = os.path.join(scratch, "cache")
@@ -395,6 +415,74 @@ def cpu_baseline_extras(ref, budget_s=6.0):
 
 
 HW_QUEUES_DEFAULT = "2"
+DUMP_MAX_BYTES = 64 * 2 ** 20   # --dump-outputs: the whole dump stays below this
+PARAM_SAMPLE = 4096             # --dump-outputs: elements sampled from each parameter tensor larger than this
+
+
+def host_array(t):
+    """a tensor as a numpy array for --dump-outputs: float64 when the tensor is float64 or integer, float32 otherwise"""
+    import torch
+    t = t.detach()
+    wide = t.dtype == torch.float64 or not (t.dtype.is_floating_point or t.dtype == torch.bool)
+    return t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+
+
+def step_outputs(losses, model):
+    """--dump-outputs, training: what one training step leaves its caller, on the host — every loss, and the trainable
+    parameters it updated.  A parameter tensor larger than PARAM_SAMPLE elements is sampled at PARAM_SAMPLE fixed flat
+    (logical NCHW) indices drawn from a generator seeded by the parameter's name: the same elements in every run and on
+    every layout.  Must run before any further step changes the parameters."""
+    import zlib
+
+    import torch
+    out = {k: host_array(v) for k, v in losses.items()}
+    for name, p in getattr(model, "module", model).named_parameters():
+        if not p.requires_grad:
+            continue
+        flat = p.detach().reshape(-1)
+        if flat.numel() > PARAM_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(flat.numel(), (PARAM_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        out["param." + name] = host_array(flat)
+    return out
+
+
+def seeded_step_outputs(cfg, device, layout, batch):
+    """--dump-outputs, training: the training step the timed region runs, run once more from the bench's seeded initial
+    state (a fresh model, optimizer and RNG stream, seed 1234 as rank 0's) on the last timed step's batch -> step_outputs.
+    The timed steps' own results differ between runs: MIOpen's channels-last convolution solvers add partial sums with
+    atomics, in an order that changes from run to run, and each training step carries those last-bit differences into
+    the next.  This step's inputs are the same in every run, so its outputs differ by rounding only."""
+    import torch
+    from maskrcnn_benchmark.engine.bench_step import build_training
+    torch.manual_seed(1234)
+    model, _, _, step = build_training(cfg, device, layout=layout)
+    losses = step(*batch)
+    torch.cuda.synchronize(device)
+    return step_outputs(losses, model)
+
+
+def detection_outputs(dets):
+    """--dump-outputs, --eval: every field of every image's detections (BoxList) -> {"det<i>.<field>": array}"""
+    out = {}
+    for i, d in enumerate(dets):
+        out["det%d.bbox" % i] = host_array(d.bbox)
+        for k, v in d.extra_fields.items():
+            out["det%d.%s" % (i, k)] = host_array(v)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """write {name: array} as out_dir/<name>.npy; refuses a dump larger than DUMP_MAX_BYTES"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays)
 
 
 def mask_slots_report(model):
@@ -529,6 +617,8 @@ def stub_main(args):
     for i in range(args.warmup):
         step(*batches[i % 2])
     elapsed, host_elapsed, out = timed_steps(step, batches, args.steps, sync, distributed, device)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: host_array(v) for k, v in out.items()})
     if rank == 0:
         images = args.images_per_gpu * world * args.steps
         print(json.dumps({"metric": "STUB (bench.py --stub-step: launch-logic test, not a measurement)",
@@ -581,6 +671,8 @@ def eval_main(args, cfg, device, layout, miopen_db, hw_queues, progress):
         det = step(*batches[i % len(batches)])
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, detection_outputs(det))
     images = args.images_per_gpu * args.steps
     counts = [len(d) for d in det]
     finite = all(bool(torch.isfinite(d.bbox).all()) and bool(torch.isfinite(d.get_field("scores")).all()) for d in det)
@@ -779,6 +871,10 @@ def main():
         progress("20 steps with the fixed mask-head quota done (outside the timed region)")
     gpu_phase_s = time.perf_counter() - gpu_t0
     loss_vals = {k: float(v.detach()) for k, v in losses.items()} if losses else {}
+    if rank == 0 and args.dump_outputs:
+        batch = batches[(args.steps - 1) % len(batches)]
+        progress("%d outputs of the seeded step written to %s"
+                 % (dump_outputs(args.dump_outputs, seeded_step_outputs(cfg, device, layout, batch)), args.dump_outputs))
     # N > 1 diagnosis (VERDICT r05 #4b): every rank's communication path and its exposed all-reduce time, gathered on rank 0
     ddp_ranks = None
     if distributed:

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,14 +61,94 @@ def test_world_size_mismatch_fails_loudly():
     assert r.returncode != 0 and "--gpus 1 but WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_steps_set_the_timed_steps_and_dump_outputs_writes_the_last_one(tmp_path):
+    """--steps K runs exactly K timed steps (ms_per_step = the region / K); --dump-outputs writes the last timed step's result,
+    the same file in every run with the same arguments; --steps below 1 is refused"""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--stub-step",
+                            "--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _json_line(r.stdout)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["ranks_seen.npy"]
+        dumps.append(np.load(d / "ranks_seen.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].tolist() == [1.0]
+    assert np.array_equal(dumps[0], dumps[1])
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0", "--stub-step"], env=_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+def test_step_outputs_samples_parameters_at_fixed_indices(tmp_path):
+    """bench.py::step_outputs: the losses whole, every trainable parameter whole up to PARAM_SAMPLE elements and sampled at
+    the same indices in every call above that, frozen parameters left out; dump_outputs refuses more than DUMP_MAX_BYTES"""
+    torch = pytest.importorskip("torch")
+    sys.path.insert(0, ROOT)
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(100, 100), torch.nn.Linear(100, 3))
+    model[1].bias.requires_grad_(False)
+    losses = {"loss_a": torch.tensor(0.5), "loss_b": torch.tensor(1.25, dtype=torch.float64)}
+    out = bench.step_outputs(losses, model)
+    assert sorted(out) == ["loss_a", "loss_b", "param.0.bias", "param.0.weight", "param.1.weight"]
+    assert out["loss_a"].dtype == np.float32 and out["loss_b"].dtype == np.float64
+    assert out["param.0.weight"].shape == (bench.PARAM_SAMPLE,) and out["param.0.weight"].dtype == np.float32
+    assert np.array_equal(out["param.1.weight"], model[1].weight.detach().reshape(-1).numpy())
+    assert np.isin(out["param.0.weight"], model[0].weight.detach().numpy()).all()
+    again = bench.step_outputs(losses, model)
+    assert all(np.array_equal(out[k], again[k]) for k in out)
+    assert bench.dump_outputs(str(tmp_path), out) == len(out)
+    assert np.array_equal(np.load(tmp_path / "param.0.weight.npy"), out["param.0.weight"])
+    with pytest.raises(SystemExit, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+
+
+def test_shipped_miopen_db_from_a_read_only_checkout_is_copied_writable(tmp_path, monkeypatch):
+    """bench.py::setup_miopen_db: MIOpen writes lock files, journals and records beside the databases it is pointed at, so the
+    scratch copy of the shipped database must be writable even when the checkout is read-only (modes are not copied)"""
+    import stat
+    import tempfile
+    sys.path.insert(0, ROOT)
+    import bench
+    root = tmp_path / "checkout"
+    shipped = root / "maskrcnn-benchmark_amd" / "miopen_db"
+    (shipped / "db").mkdir(parents=True)
+    (shipped / "cache").mkdir()
+    (shipped / "db" / "gfx950100.HIP.udb.txt").write_text("key=solver:params\n")
+    (shipped / "cache" / "gfx950100.ukdb").write_bytes(b"SQLite format 3\0")
+    for d, dirs, files in os.walk(root, topdown=False):
+        for f in files:
+            os.chmod(os.path.join(d, f), 0o444)
+        os.chmod(d, 0o555)
+    scratch = tmp_path / "tmp"
+    scratch.mkdir()
+    monkeypatch.setattr(bench, "ROOT", str(root))
+    monkeypatch.setattr(tempfile, "tempdir", str(scratch))
+    monkeypatch.delenv("MIOPEN_USER_DB_PATH", raising=False)
+    monkeypatch.delenv("MIOPEN_CUSTOM_CACHE_DIR", raising=False)
+    try:
+        assert bench.setup_miopen_db(None) == "shipped:" + str(shipped)
+        db, cache = os.environ["MIOPEN_USER_DB_PATH"], os.environ["MIOPEN_CUSTOM_CACHE_DIR"]
+        assert db.startswith(str(scratch)) and cache.startswith(str(scratch))
+        assert open(os.path.join(db, "gfx950100.HIP.udb.txt")).read() == "key=solver:params\n"
+        assert open(os.path.join(cache, "gfx950100.ukdb"), "rb").read() == b"SQLite format 3\0"
+        for p in (db, cache, os.path.join(db, "gfx950100.HIP.udb.txt"), os.path.join(cache, "gfx950100.ukdb")):
+            assert os.stat(p).st_mode & stat.S_IWUSR, p
+    finally:
+        for d, dirs, files in os.walk(root):
+            os.chmod(d, 0o755)
+
+
 def test_hw_queue_pin_and_sampling_cap():
     sys.path.insert(0, ROOT)
     import bench
     old = os.environ.pop("GPU_MAX_HW_QUEUES", None)
     try:
         assert bench.pin_hip_queues() == bench.HW_QUEUES_DEFAULT == os.environ["GPU_MAX_HW_QUEUES"]
-        os.environ["GPU_MAX_HW_QUEUES"] = "4"
-        assert bench.pin_hip_queues() == "4"      # an explicit setting wins
+        os.environ["GPU_MAX_HW_QUEUES"] = "1"
+        assert bench.pin_hip_queues() == "1"      # an explicit setting wins
     finally:
         os.environ.pop("GPU_MAX_HW_QUEUES", None)
         if old is not None:
