@@ -35,7 +35,7 @@ template <> struct BaIo<__hip_bfloat16> {
 };
 template <typename T> struct alignas(sizeof(T) * kBaV) BaVec { T v[kBaV]; };
 
-// g = relu ? (y > 0 ? gy : 0) : gy ;  grad_x = g ;  partial[block][c] = sum over the block's rows of g[., c]  (fp32 sums;
+// g = relu ? (y <= 0 ? 0 : gy) : gy ;  grad_x = g ;  partial[block][c] = sum over the block's rows of g[., c]  (fp32 sums;
 // T = float | __half | __hip_bfloat16 storage: the autocast configurations)
 template <typename T, bool kRelu>
 __global__ void __launch_bounds__(kBaThreads)
@@ -55,7 +55,7 @@ bias_act_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, T* _
       const VT m = yv[i];
 #pragma unroll
       for (int j = 0; j < kBaV; ++j)
-        if (!(BaIo<T>::ld(m.v[j]) > 0.f)) g.v[j] = BaIo<T>::st(0.f);
+        if (BaIo<T>::ld(m.v[j]) <= 0.f) g.v[j] = BaIo<T>::st(0.f);   // threshold_backward: passes where y is NaN
       xo[i] = g;
     } else if (gx != gy) {
       xo[i] = g;

@@ -7,9 +7,11 @@ constexpr int kSpinBudget = 1 << 22;   // polls before a wait on another workgro
 
 // ---- the device primitives.  This is the ONE place in the library sources that knows about the host emulation
 // (tests/emu compiles the kernels as host C++ for logic checks without a GPU): there, every name defined between
-// here and the #endif comes from tests/emu/detops_emu_shims.h instead.
+// here and the #endif comes from tests/emu/detops_emu_shims.h instead, except DETOPS_F32_VALUE, defined as a no-op below.
 #ifdef DETOPS_CPU_EMU
 #include "detops_emu_shims.h"
+// (host C++ has no instruction selection to steer)
+#define DETOPS_F32_VALUE(x) ((void)0)
 #else
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -44,6 +46,9 @@ constexpr int kSpinBudget = 1 << 22;   // polls before a wait on another workgro
 // the same for three values, one of which only SOME paths below use: the compiler can neither sink that load under the
 // branch nor wait for the three one by one — the requests go out together, one round trip
 #define DETOPS_KEEP_TOGETHER3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
+// `x` exists as an fp32 value here: a later narrowing of `a * b` to __half is otherwise selected as ONE v_fma_mixlo_f16
+// (a single rounding of the exact product), which differs from the fp32 product + cast on ties.  No instruction is emitted.
+#define DETOPS_F32_VALUE(x) asm("" : "+v"(x))
 
 // Ordering point for LDS data handed from some lanes of a wave to other lanes of the SAME wave (no other wave
 // touches the region): the hardware executes a wave's LDS operations in order, so only the compiler must be kept

@@ -54,14 +54,14 @@ frozen_bn_fwd_kernel(const T* __restrict__ x, const float* __restrict__ scale, c
     for (int j = 0; j < V; ++j) {
       float t = Cvt<T>::load(a.v[j]) * s + b;       // torch: (x * scale) + bias, two roundings in fp32
       if (kRes) t = t + Cvt<T>::load(r.v[j]);
-      if (kRelu) t = t > 0.f ? t : 0.f;
+      if (kRelu) t = t <= 0.f ? 0.f : t;         // torch.relu: NaN stays NaN
       o.v[j] = Cvt<T>::store(t);
     }
     yv[i] = o;
   }
 }
 
-// g = relu ? (y > 0 ? gy : 0) : gy ;  grad_x = g * scale[c] ;  grad_res = g (optional)
+// g = relu ? (y <= 0 ? 0 : gy) : gy ;  grad_x = g * scale[c] ;  grad_res = g (optional)
 template <typename T, int V, bool kRelu, bool kRes>
 __global__ void __launch_bounds__(kThreads)
 frozen_bn_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ y, const float* __restrict__ scale,
@@ -83,8 +83,10 @@ frozen_bn_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ y, const fl
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float t = Cvt<T>::load(g.v[j]);
-      if (kRelu && !(Cvt<T>::load(m.v[j]) > 0.f)) t = 0.f;
-      ox.v[j] = Cvt<T>::store(t * s);
+      if (kRelu && Cvt<T>::load(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
+      float p = t * s;
+      DETOPS_F32_VALUE(p);                            // fp32 product, then the cast: torch's `(g * s).to(T)`
+      ox.v[j] = Cvt<T>::store(p);
       if (kRes) orr.v[j] = Cvt<T>::store(t);
     }
     xo[i] = ox;
@@ -126,7 +128,7 @@ frozen_bn_fwd_nhwc_kernel(const T* __restrict__ x, const float* __restrict__ sca
     for (int j = 0; j < V; ++j) {
       float t = Cvt<T>::load(a.v[j]) * s[j] + b[j];
       if (kRes) t = t + Cvt<T>::load(r.v[j]);
-      if (kRelu) t = t > 0.f ? t : 0.f;
+      if (kRelu) t = t <= 0.f ? 0.f : t;         // torch.relu: NaN stays NaN
       o.v[j] = Cvt<T>::store(t);
     }
     yv[i] = o;
@@ -162,8 +164,10 @@ frozen_bn_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, con
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float t = Cvt<T>::load(g.v[j]);
-      if (kRelu && !(Cvt<T>::load(m.v[j]) > 0.f)) t = 0.f;
-      ox.v[j] = Cvt<T>::store(t * s[j]);
+      if (kRelu && Cvt<T>::load(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
+      float p = t * s[j];
+      DETOPS_F32_VALUE(p);
+      ox.v[j] = Cvt<T>::store(p);
       if (kRes) orr.v[j] = Cvt<T>::store(t);
     }
     xo[i] = ox;

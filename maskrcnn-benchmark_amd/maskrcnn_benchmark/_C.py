@@ -1298,7 +1298,7 @@ class _BiasAct(torch.autograd.Function):
         N, C, H, W = gy.shape
         rows = N * H * W
         if not ctx.fused:
-            gx = gy * (y > 0) if ctx.relu else gy
+            gx = torch.ops.aten.threshold_backward(gy, y, 0) if ctx.relu else gy      # relu's backward (NaN y passes)
             return gx, column_sum(gx.permute(0, 2, 3, 1).reshape(rows, C)), None    # (a view of the channels-last storage)
         gb = torch.empty((C,), dtype=torch.float32, device=gy.device)
         gx = torch.empty_like(gy) if ctx.relu else gy

@@ -1240,6 +1240,10 @@ def test_frozen_bn_fused_half(dtype):
     ref = torch.relu(bn(x) + r)
     out = bn.fused(x.to(dtype), relu=True, residual=r.to(dtype)).float()
     assert (out - ref).abs().max() <= 2e-2 * ref.abs().max()
+    # and bit-equal to the fp32 composition on the same rounded inputs with the module's folded constants (one rounding)
+    scale, bias = (t.cpu().reshape(1, -1, 1, 1) for t in bn.folded())
+    want = torch.relu(x.to(dtype).cpu().float() * scale + bias + r.to(dtype).cpu().float()).to(dtype)
+    assert torch.equal(out.to(dtype).cpu(), want)
 
 
 @pytest.mark.parametrize("shape", CFG5_SHAPES)

@@ -527,3 +527,12 @@ def test_float64_operators_equal_the_float32_oracle_and_the_reference_semantics(
     bx, sc = synth.nms_boxes(500, seed=9)
     keep = _C.nms(_t(bx).double(), _t(sc).double(), 0.6)
     assert keep.dtype == torch.int64 and np.array_equal(keep.numpy(), oracle.nms(bx, sc, 0.6))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("channels_last", [False, True])
+def test_fused_relu_keeps_nan_like_torch_relu(dtype, channels_last):
+    """the fused ReLU of FrozenBatchNorm2d.fused and _C.bias_act on NaN / +-inf / -0.0 / inf + (-inf): forward = torch.relu
+    (NaN stays NaN), backward = aten.threshold_backward (the gradient passes where y is NaN) — tests/torch_refs.py"""
+    import torch_refs
+    torch_refs.check_fused_relu_non_finite("cpu", dtype, channels_last)

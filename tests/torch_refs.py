@@ -194,3 +194,79 @@ def deform_psroi_pool_torch(data, rois, trans, no_trans, scale, output_dim, grou
         z = data.new_zeros((0, output_dim, P, P))
         return z, z
     return torch.stack(outs), torch.stack(cnts)
+
+
+# ---------------------------------------------------------------------------------------------- fused ReLU, non-finite values
+def _exact(got, want, what):
+    """same dtype, same NaN positions, every other element equal (+0 == -0)"""
+    assert got.dtype == want.dtype, (what, got.dtype, want.dtype)
+    torch.testing.assert_close(got, want, rtol=0, atol=0, equal_nan=True, msg=lambda m: "%s: %s" % (what, m))
+
+
+def check_fused_relu_non_finite(device, dtype, channels_last):
+    """The fused ReLU of FrozenBatchNorm2d.fused (csrc/frozen_bn.hip) and of _C.bias_act (csrc/bias_act.hip) follows
+    torch.relu on non-finite values: NaN stays NaN in the forward, and the backward is aten.threshold_backward(g, y, 0),
+    which passes the gradient where y is NaN.  Inputs hold NaN, +-inf, -0.0 and inf + (-inf) through the residual; the
+    reference is the fp32 composition on the same dtype-rounded values, one rounding at the end."""
+    from maskrcnn_benchmark import _C
+    from maskrcnn_benchmark.layers import FrozenBatchNorm2d
+    N, C, H, W = 2, 8, 4, 6
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    g = torch.Generator().manual_seed(11 + int(channels_last))
+    inf, nan = float("inf"), float("nan")
+    x = torch.randn(N, C, H, W, generator=g)
+    r = torch.randn(N, C, H, W, generator=g)
+    x[:, :, 0, :5] = torch.tensor([nan, inf, -inf, -0.0, 0.0])
+    x[:, :, 1, :4] = torch.tensor([inf, -inf, 1.0, inf])
+    r[:, :, 1, :4] = torch.tensor([-inf, inf, nan, inf])          # inf + (-inf) = NaN, NaN residual, inf + inf
+    r[:, :, 2, :2] = torch.tensor([-0.0, -inf])
+    x, r = x.to(dtype), r.to(dtype)
+    gy = torch.randn(N, C, H, W, generator=g).to(dtype)
+
+    bn = FrozenBatchNorm2d(C)
+    bn.weight.copy_(torch.linspace(-1.5, 1.5, C))                 # signed scales: +-inf swap sign in some channels
+    bn.bias.copy_(torch.randn(C, generator=g))
+    bn.running_mean.copy_(torch.randn(C, generator=g))
+    bn.running_var.copy_(torch.rand(C, generator=g) + 0.3)
+    bn = bn.to(device)
+    scale, bias = (t.cpu().reshape(1, -1, 1, 1) for t in bn.folded())
+    for res in (False, True):
+        xd = x.to(device).clone(memory_format=fmt).requires_grad_()
+        rd = r.to(device).clone(memory_format=fmt).requires_grad_() if res else None
+        y = bn.fused(xd, relu=True, residual=rd)
+        y.backward(gy.to(device).contiguous(memory_format=fmt))
+        assert _C.is_channels_last(y) == channels_last and _C.is_channels_last(xd.grad) == channels_last
+        t = x.float() * scale + bias
+        if res:
+            t = t + r.float()
+        want = torch.relu(t).to(dtype)
+        assert int(want.isnan().sum()) > 0 and int(torch.isinf(want).sum()) > 0
+        _exact(y.detach().cpu(), want, "frozen_bn forward res=%d" % res)
+        m = torch.ops.aten.threshold_backward(gy.float(), want.float(), 0)
+        _exact(xd.grad.cpu(), (m * scale).to(dtype), "frozen_bn grad_x res=%d" % res)
+        if res:
+            _exact(rd.grad.cpu(), m.to(dtype), "frozen_bn grad_residual")
+
+    if not channels_last:
+        return
+    # bias_act: the FrozenBN stream with scale 1 forward; its own backward pass (mask, grad_x, fp32 column sums).  C = 8 takes
+    # the fused kernels, C = 12 the generic path (in-place add + column_sum).
+    for Cb in (8, 12):
+        xb = torch.cat([x, x[:, :Cb - C]], 1) if Cb > C else x
+        gb = torch.cat([gy, gy[:, :Cb - C]], 1) if Cb > C else gy
+        b = torch.randn(Cb, generator=g)
+        xd = xb.to(device).clone(memory_format=torch.channels_last).requires_grad_()
+        bd = b.to(device).clone().requires_grad_()
+        y = _C.bias_act(xd.clone(memory_format=torch.channels_last), bd, True)
+        y.backward(gb.to(device).contiguous(memory_format=torch.channels_last))
+        # (the generic path adds the bias in the activation's dtype, as the convolution's own bias would)
+        bias_as = b if Cb == 8 else b.to(dtype).float()
+        want = torch.relu(xb.float() + bias_as.reshape(1, -1, 1, 1)).to(dtype)
+        _exact(y.detach().cpu(), want, "bias_act forward C=%d" % Cb)
+        m = torch.ops.aten.threshold_backward(gb.float(), want.float(), 0)
+        _exact(xd.grad.cpu(), m.to(dtype), "bias_act grad_x C=%d" % Cb)
+        terms = m.double()
+        # fp32 sums of n terms in any order: |error| <= n * eps32 * sum |terms|
+        colsum, bound = terms.sum((0, 2, 3)), terms[:, 0].numel() * 2.0 ** -24 * terms.abs().sum((0, 2, 3))
+        got = bd.grad.cpu().double()
+        assert bool(((got - colsum).abs() <= bound).all()), ("bias_act grad_bias C=%d" % Cb, got, colsum)
