@@ -526,6 +526,41 @@ int detops_mask_loss_f32(const float* mask_logits, const int64_t* labels, const 
 int detops_head_loss_backward_f32(float* grad_a, int64_t count_a, const float* upstream_a, float* grad_b, int64_t count_b,
                                   const float* upstream_b, detops_stream_t stream);
 
+/* ---- keypoint head (csrc/keypoint.hip) ---------------------------------------------------------------------------------
+ * detops_keypoint_targets — KeypointRCNNLossComputation.prepare_targets + keypoints_to_heat_map (reference
+ *   roi_heads/keypoint_head/loss.py:79-100, 145-157; structures/keypoint.py:154-188) for the whole batch in one launch:
+ *   boxes [P, 4] xyxy (the slots), matched [P] int64 (row of gt_boxes / gt_keypoints, global across the images; < 0 = none),
+ *   labels [P] int64 (> 0 = positive slot), gt_boxes [G, 4] xyxy, gt_keypoints [G, K, 3] (x, y, v).  Per (p, k):
+ *   x -> floor((x - x1) * ((1 / (x2 - x1)) * M)) in fp32 without contraction (torch's `M / t` is reciprocal() * M),
+ *   x == x2 -> M - 1, the same for y;
+ *   valid[p, k] = 0 <= x, y < M  and  v > 0  and  labels[p] > 0  and  gt matched[p] has a keypoint with v > 0 inside its own
+ *   box (inclusive edges, loss.py:40-53, 93-98); heatmaps[p, k] = valid ? y * M + x : 0.  heatmaps [P, K] int64,
+ *   valid [P, K] uint8.  Bit-equal to the torch formulation.
+ * detops_keypoint_loss_f32 — KeypointRCNNLossComputation.__call__ (loss.py:145-169): logits [P, K, H, W] read through the
+ *   HOST array logit_strides[4] (elements; NCHW and channels-last alike), heatmaps [P, K] int64 (target pixel y * W + x of
+ *   each row), valid [P, K] uint8.  loss1 = sum over the valid rows of the softmax cross-entropy of the row's H * W logits
+ *   / max(#valid, 1) — the count formed on the device; 0 without valid rows.  grad_logits (strides grad_strides[4]) fully
+ *   written: d loss1 / d logits, 0 on invalid rows.  Accumulation in fp32, sums in a fixed order.  Three launches: the
+ *   count, one workgroup per (ROI, keypoint) row (per ROI when the keypoint stride is 1, channels-last), the final
+ *   sum; workspace (P * K + 1) floats.
+ * detops_heatmaps_to_keypoints_f32 — heatmaps_to_keypoints (roi_heads/keypoint_head/inference.py:40-94) for every
+ *   detection of the batch: heatmaps [N, K, H, W] (H * W <= 4096) read through the HOST array strides[4], boxes [N, 4]
+ *   xyxy.  Per (n, k): the map resized to ceil(max(w, 1)) x ceil(max(h, 1)) with OpenCV's INTER_CUBIC (A = -0.75,
+ *   source (d + 0.5) * in / out - 0.5, border taps clamped, horizontal then vertical pass, fp32), its argmax (row-major,
+ *   first maximum) and the value there.  keypoints [N, K, 3] = ((x_int + 0.5) * (w / ceil(w)) + x1, likewise y, 1),
+ *   evaluated in fp64 and rounded once to fp32 (numpy's promotion); scores [N, K] = the maximum.  The resized map is
+ *   never stored. */
+int detops_keypoint_targets(const float* boxes, const int64_t* matched, const int64_t* labels, const float* gt_boxes,
+                            const float* gt_keypoints, int P, int G, int K, int M, int64_t* heatmaps, unsigned char* valid,
+                            detops_stream_t stream);
+size_t detops_keypoint_loss_workspace_bytes(int P, int K);
+int detops_keypoint_loss_f32(const float* logits, const int64_t* logit_strides, const int64_t* heatmaps,
+                             const unsigned char* valid, int P, int K, int H, int W, float* grad_logits,
+                             const int64_t* grad_strides, float* loss1, void* workspace, size_t workspace_bytes,
+                             detops_stream_t stream);
+int detops_heatmaps_to_keypoints_f32(const float* heatmaps, const int64_t* strides, const float* boxes, int N, int K, int H,
+                                     int W, float* keypoints, float* scores, detops_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused FrozenBatchNorm2d affine (+ residual) (+ ReLU) — the elementwise tail of every backbone
  * convolution: layers/batch_norm.py:19-31 (`x * scale + bias`), then `F.relu_`, and in the

@@ -578,7 +578,24 @@ def _mask_loss_forward(aux, mask_logits, labels, mask_targets):
     return (g,), out
 
 
-_HEAD_LOSS = {"fastrcnn": _fastrcnn_loss_forward, "mask": _mask_loss_forward}
+def _strides4(t):
+    return (ctypes.c_int64 * 4)(*t.stride())
+
+
+def _keypoint_loss_forward(aux, logits, heatmaps, valid):
+    P, K, H, W = logits.shape
+    dev = logits.device
+    g = torch.empty_like(logits)
+    out = torch.empty((1,), dtype=torch.float32, device=dev)
+    nbytes = int(lib.detops_keypoint_loss_workspace_bytes(P, K))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with _on_device(logits), _timed(("keypoint_loss[P=%d,K=%d,M=%d]", (P, K, H)), logits):
+        check(lib.detops_keypoint_loss_f32(ptr(logits), _strides4(logits), ptr(heatmaps), ptr(valid), P, K, H, W, ptr(g),
+                                           _strides4(g), ptr(out), ptr(ws), nbytes, stream_of(logits)), "keypoint_loss")
+    return (g,), out
+
+
+_HEAD_LOSS = {"fastrcnn": _fastrcnn_loss_forward, "mask": _mask_loss_forward, "keypoint": _keypoint_loss_forward}
 
 
 def fastrcnn_loss(class_logits, box_regression, labels, regression_targets, cls_agnostic=False, beta=1.0):
@@ -609,6 +626,57 @@ def mask_loss(mask_logits, labels, mask_targets):
     if P == 0 or M != M2 or labels.shape != (P,) or mask_targets.shape != (P, M, M):
         raise ValueError("mask_loss: inconsistent arguments")
     return _HeadLoss.apply("mask", None, mask_logits, labels, mask_targets)[0]
+
+
+def keypoint_loss(keypoint_logits, heatmaps, valid):
+    """Keypoint-head loss, value + gradient in one pass (extension; reference roi_heads/keypoint_head/loss.py:145-169):
+    keypoint_logits [P,K,H,W] fp32 (NCHW or channels-last: read through its strides, no copy), heatmaps [P,K] int64 target
+    pixel, valid [P,K] bool -> mean softmax cross-entropy of the valid rows (0 without valid rows; the count never leaves
+    the device)."""
+    _need_cuda("keypoint_loss", keypoint_logits, heatmaps, valid)
+    if keypoint_logits.dtype != torch.float32:
+        raise RuntimeError("keypoint_loss: expected a float32 tensor, got %s" % keypoint_logits.dtype)
+    P, K, H, W = keypoint_logits.shape
+    if P == 0 or heatmaps.shape != (P, K) or valid.shape != (P, K):
+        raise ValueError("keypoint_loss: inconsistent arguments")
+    heatmaps = heatmaps.to(torch.int64).contiguous()
+    return _HeadLoss.apply("keypoint", None, keypoint_logits, heatmaps, _u8("keypoint_loss", valid))[0]
+
+
+def keypoint_targets(boxes, matched, labels, gt_boxes, gt_keypoints, heatmap_size):
+    """Keypoint-head targets of every slot of the batch in one launch (extension; reference
+    roi_heads/keypoint_head/loss.py:79-100 + structures/keypoint.py:154-188): boxes [P,4] xyxy, matched [P] int64 (row of
+    gt_boxes [G,4] / gt_keypoints [G,K,3], global across the images, < 0 = none), labels [P] int64 -> (heatmaps [P,K] int64,
+    valid [P,K] bool), bit-equal to the torch formulation."""
+    _need_cuda("keypoint_targets", boxes, matched, labels, gt_boxes, gt_keypoints)
+    boxes, gt_boxes = _f32c("keypoint_targets", boxes), _f32c("keypoint_targets", gt_boxes)
+    gt_keypoints = _f32c("keypoint_targets", gt_keypoints)
+    matched, labels = matched.to(torch.int64).contiguous(), labels.to(torch.int64).contiguous()
+    P, (G, K, _) = boxes.shape[0], gt_keypoints.shape
+    M = int(heatmap_size)
+    heat = torch.empty((P, K), dtype=torch.int64, device=boxes.device)
+    valid = torch.empty((P, K), dtype=torch.uint8, device=boxes.device)
+    if P:
+        with _on_device(boxes), _timed(("keypoint_targets[P=%d,K=%d,M=%d]", (P, K, M)), boxes):
+            check(lib.detops_keypoint_targets(ptr(boxes), ptr(matched), ptr(labels), ptr(gt_boxes), ptr(gt_keypoints), P, G, K,
+                                              M, ptr(heat), ptr(valid), stream_of(boxes)), "keypoint_targets")
+    return heat, valid.view(torch.bool)
+
+
+def heatmaps_to_keypoints(heatmaps, boxes):
+    """Keypoint decoding of every detection of the batch (extension; reference roi_heads/keypoint_head/inference.py:40-94):
+    heatmaps [N,K,H,W] (any strides), boxes [N,4] xyxy -> (keypoints [N,K,3] = (x, y, 1), scores [N,K]); the bicubic
+    resize to the box size is evaluated in place, never stored."""
+    _need_cuda("heatmaps_to_keypoints", heatmaps, boxes)
+    heatmaps, boxes = heatmaps.float(), _f32c("heatmaps_to_keypoints", boxes)
+    N, K, H, W = heatmaps.shape
+    kps = torch.empty((N, K, 3), dtype=torch.float32, device=boxes.device)
+    scores = torch.empty((N, K), dtype=torch.float32, device=boxes.device)
+    if N:
+        with _on_device(boxes), _timed(("heatmaps_to_keypoints[N=%d,K=%d]", (N, K)), boxes):
+            check(lib.detops_heatmaps_to_keypoints_f32(ptr(heatmaps), _strides4(heatmaps), ptr(boxes), N, K, H, W, ptr(kps),
+                                                       ptr(scores), stream_of(boxes)), "heatmaps_to_keypoints")
+    return kps, scores
 
 
 # ------------------------------------------------------------------------------------------ target assignment

@@ -6,7 +6,9 @@ data/transforms/build.py:5-42, data/collate_batch.py:5-20):
   image   float32 [3, H, W] (unit-variance noise), H x W = a COCO-like size after the
           min-800 / max-1333 resize (default 800 x 1333 -> padded to 800 x 1344 by the collator);
   target  BoxList (xyxy, size (W, H)) with fields "labels" int64 in 1..80 and "masks"
-          SegmentationMask (binary, filled ellipses inscribed in the boxes), 8-20 objects.
+          SegmentationMask (binary, filled ellipses inscribed in the boxes), 8-20 objects; with
+          `with_keypoints` also "keypoints" PersonKeypoints [n, 17, 3]: most points inside their box with
+          v = 1 or 2, some unlabelled (v = 0, x = y = 0), a few just outside the box.
 
 Samples are a pure function of (seed, index): every rank / worker regenerates the same item.
 """
@@ -17,16 +19,18 @@ import torch.utils.data
 
 from maskrcnn_benchmark.structures.bounding_box import BoxList
 from maskrcnn_benchmark.structures.image_list import to_image_list
+from maskrcnn_benchmark.structures.keypoint import PersonKeypoints
 from maskrcnn_benchmark.structures.segmentation_mask import SegmentationMask
 
 
 class SyntheticCOCODataset(torch.utils.data.Dataset):
     def __init__(self, length=1024, height=800, width=1333, num_classes=81, min_objects=8, max_objects=20,
-                 with_masks=True, seed=0, pixel_std=1.0):
+                 with_masks=True, seed=0, pixel_std=1.0, with_keypoints=False):
         self.length, self.height, self.width = length, height, width
         self.num_classes = num_classes
         self.min_objects, self.max_objects = min_objects, max_objects
         self.with_masks = with_masks
+        self.with_keypoints = with_keypoints
         self.seed = seed
         # unit-variance pixels: with random-init weights and frozen (identity) batch-norm the
         # activations keep the input scale, so COCO's ~58-unit pixel std would blow the losses up
@@ -58,8 +62,27 @@ class SyntheticCOCODataset(torch.utils.data.Dataset):
             ell = (((xx - cx[:, None, None]) / (bw[:, None, None] / 2)) ** 2 +
                    ((yy - cy[:, None, None]) / (bh[:, None, None] / 2)) ** 2) <= 1.0
             target.add_field("masks", SegmentationMask(ell.to(torch.uint8), (W, H), mode="mask"))
+        if self.with_keypoints:
+            # drawn after every other draw of the sample: the images and boxes are those of a config without keypoints
+            target.add_field("keypoints", PersonKeypoints(_draw_keypoints(boxes, g), (W, H)))
         target = target.clip_to_image(remove_empty=True)
         return image, target, index
+
+
+def _draw_keypoints(boxes, g, K=17):
+    """boxes [n, 4] xyxy -> [n, K, 3] (x, y, v): positions uniform over the box, 5 % of them up to 8 % of the box side
+    outside it; v = 2 (60 %), 1 (25 %) or 0 (15 %, then x = y = 0, the COCO convention)"""
+    n = boxes.shape[0]
+    u = torch.rand(n, K, 2, generator=g)
+    out = torch.rand(n, K, generator=g) < 0.05
+    push = torch.rand(n, K, 2, generator=g) * 0.08
+    u = torch.where(out[..., None], torch.where(u < 0.5, -push, 1.0 + push), u)
+    lo, side = boxes[:, None, :2], (boxes[:, 2:] - boxes[:, :2])[:, None, :]
+    xy = lo + u * side
+    r = torch.rand(n, K, generator=g)
+    v = torch.where(r < 0.15, 0.0, torch.where(r < 0.40, 1.0, 2.0))
+    xy = torch.where((v == 0)[..., None], torch.zeros_like(xy), xy)
+    return torch.cat([xy, v[..., None]], dim=2)
 
 
 class BatchCollator(object):
@@ -86,6 +109,6 @@ def make_data_loader(cfg, is_train=True, is_distributed=False, start_iter=0, ima
     max_size = cfg.INPUT.MAX_SIZE_TRAIN if is_train else cfg.INPUT.MAX_SIZE_TEST
     ds = SyntheticCOCODataset(length=length or max(cfg.SOLVER.MAX_ITER * images_per_gpu, 64), height=size,
                               width=max_size, num_classes=cfg.MODEL.ROI_BOX_HEAD.NUM_CLASSES,
-                              with_masks=cfg.MODEL.MASK_ON, seed=get_rank())
+                              with_masks=cfg.MODEL.MASK_ON, seed=get_rank(), with_keypoints=cfg.MODEL.KEYPOINT_ON)
     return torch.utils.data.DataLoader(ds, batch_size=images_per_gpu, shuffle=False,
                                        num_workers=0, collate_fn=BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY))

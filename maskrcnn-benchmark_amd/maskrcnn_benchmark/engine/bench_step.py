@@ -77,7 +77,8 @@ def make_device_batches(cfg, device, images_per_gpu=2, num_batches=2, seed=0, he
     H = height or cfg.INPUT.MIN_SIZE_TRAIN[0]
     W = width or cfg.INPUT.MAX_SIZE_TRAIN
     ds = SyntheticCOCODataset(length=num_batches * images_per_gpu, height=H, width=W,
-                              num_classes=cfg.MODEL.ROI_BOX_HEAD.NUM_CLASSES, with_masks=cfg.MODEL.MASK_ON, seed=seed)
+                              num_classes=cfg.MODEL.ROI_BOX_HEAD.NUM_CLASSES, with_masks=cfg.MODEL.MASK_ON, seed=seed,
+                              with_keypoints=cfg.MODEL.KEYPOINT_ON)
     collate = BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)
     out = []
     for b in range(num_batches):

@@ -33,7 +33,7 @@ class GeneralizedRCNN(nn.Module):
         per level).  `heads=True`: the heads take the channels-last pyramid as it is — the RPN head's convolutions run
         channels-last (its two small outputs are handed to the proposal / loss kernels as NCHW), the poolers read the
         pyramid in place (csrc/roi_align_nhwc.hip), the box head's pooled tensor stays [K, C, 7, 7] for its FC layers and
-        the mask head (pooler output, convolutions, deconvolution) runs channels-last.  Parameters, buffers and the
+        the mask and keypoint heads (pooler output, convolutions, deconvolution) run channels-last.  Parameters, buffers and the
         state_dict are untouched (a memory format is a stride permutation, not a shape)."""
         fmt = torch.channels_last if on else torch.contiguous_format
         self.backbone.to(memory_format=fmt)
@@ -50,6 +50,11 @@ class GeneralizedRCNN(nn.Module):
                 mask.feature_extractor.to(memory_format=hfmt)
                 mask.predictor.to(memory_format=hfmt)
                 mask.feature_extractor.pooler.output_channels_last = heads
+        keypoint = self.roi_heads["keypoint"] if (self.roi_heads and "keypoint" in self.roi_heads) else None
+        if keypoint is not None:
+            keypoint.feature_extractor.to(memory_format=hfmt)
+            keypoint.predictor.to(memory_format=hfmt)
+            keypoint.feature_extractor.pooler.output_channels_last = heads
         self.channels_last = bool(on)
         self.channels_last_heads = heads
         return self

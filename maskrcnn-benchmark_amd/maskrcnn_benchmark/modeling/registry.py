@@ -19,3 +19,5 @@ ROI_BOX_FEATURE_EXTRACTORS = Registry()
 ROI_BOX_PREDICTOR = Registry()
 ROI_MASK_FEATURE_EXTRACTORS = Registry()
 ROI_MASK_PREDICTOR = Registry()
+ROI_KEYPOINT_FEATURE_EXTRACTORS = Registry()
+ROI_KEYPOINT_PREDICTOR = Registry()

@@ -1,8 +1,8 @@
-"""CombinedROIHeads (reference roi_heads/roi_heads.py:9-83); the keypoint head is a separate model
-family outside the BASELINE configs and is not built."""
+"""CombinedROIHeads (reference roi_heads/roi_heads.py:9-83): box, then mask, then keypoint head."""
 import torch
 
 from .box_head.box_head import build_roi_box_head
+from .keypoint_head.keypoint_head import build_roi_keypoint_head
 from .mask_head.mask_head import build_roi_mask_head
 
 
@@ -23,6 +23,9 @@ class CombinedROIHeads(torch.nn.ModuleDict):
                 mask_features = x
             x, detections, loss_mask = self.mask(mask_features, detections, targets)
             losses.update(loss_mask)
+        if self.cfg.MODEL.KEYPOINT_ON:
+            x, detections, loss_keypoint = self.keypoint(features, detections, targets)
+            losses.update(loss_keypoint)
         return x, detections, losses
 
 
@@ -35,5 +38,5 @@ def build_roi_heads(cfg, in_channels):
     if cfg.MODEL.MASK_ON:
         heads.append(("mask", build_roi_mask_head(cfg, in_channels)))
     if cfg.MODEL.KEYPOINT_ON:
-        raise NotImplementedError("the keypoint head is outside the hot path and is not built")
+        heads.append(("keypoint", build_roi_keypoint_head(cfg, in_channels)))
     return CombinedROIHeads(cfg, heads) if heads else []

@@ -472,6 +472,41 @@ def bench_dcn_block(C, iters):
     return out
 
 
+def bench_keypoint(C, iters):
+    """the keypoint head's kernels (csrc/keypoint.hip): targets of 2 x 256 slots against 20 ground truths; the loss at
+    P = 256, K = 17, M = 56 on NCHW and channels-last logits (bytes: logits read + gradient written = 109 MB, ~17 us at the
+    6.29 TB/s copy ceiling); decoding of 100 detections with sides log-uniform in 32-800 px (bytes: the heatmaps + outputs)"""
+    out = []
+    g = torch.Generator().manual_seed(3)
+    P, K, M, G = 512, 17, 56, 20
+    gt = torch.rand(G, 2, generator=g) * 600
+    gt = torch.cat([gt, gt + 40 + torch.rand(G, 2, generator=g) * 400], 1)
+    kp = torch.cat([gt[:, None, :2] + torch.rand(G, K, 2, generator=g) * (gt[:, None, 2:] - gt[:, None, :2]),
+                    torch.randint(0, 3, (G, K, 1), generator=g).float()], 2)
+    matched = torch.randint(0, G, (P,), generator=g)
+    boxes = gt[matched] + torch.randn(P, 4, generator=g) * 10
+    labels = torch.ones(P, dtype=torch.int64)
+    args = [a.cuda() for a in (boxes, matched, labels, gt, kp)]
+    us = dev_time_us(lambda: C.keypoint_targets(*args, M), iters)
+    out.append(_entry("keypoint_targets P=512 K=17 G=20", us, P * (16 + 8 + 8) + G * (16 + K * 12) + P * K * 9))
+    P = 256
+    logits = torch.randn(P, K, M, M, device="cuda") * 3
+    heat = torch.randint(0, M * M, (P, K), device="cuda")
+    valid = torch.rand(P, K, device="cuda") < 0.7
+    for tag, x in (("nchw", logits), ("channels-last", logits.contiguous(memory_format=torch.channels_last))):
+        us = dev_time_us(lambda: C.keypoint_loss(x, heat, valid), iters)
+        out.append(_entry("keypoint_loss value+grad P=256 K=17 M=56 %s" % tag, us, 2 * x.numel() * 4 + P * K * 9))
+    N = 100
+    s_ = torch.exp(torch.empty(N, 2).uniform_(np.log(32), np.log(800), generator=g))
+    xy = torch.rand(N, 2, generator=g) * 500
+    dets = torch.cat([xy, xy + s_], 1).cuda()
+    maps = torch.randn(N, K, M, M, generator=g).cuda()
+    us = dev_time_us(lambda: C.heatmaps_to_keypoints(maps, dets), max(5, iters // 5))
+    out.append(_entry("heatmaps_to_keypoints N=100 K=17 sides 32-800 px", us, maps.numel() * 4 + N * K * 16,
+                      {"resized_px_per_map_mean": int((s_[:, 0].ceil() * s_[:, 1].ceil()).mean())}))
+    return out
+
+
 def copy_ceiling(iters):
     a = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
     b = torch.empty_like(a)
@@ -529,6 +564,8 @@ def main():
         res += bench_nms(C, args.iters)
     if not only or "targets" in only:
         res += bench_targets(C, args.iters)
+    if not only or "keypoint" in only:
+        res += bench_keypoint(C, args.iters)
     if not only or "frozen_bn" in only:
         res += bench_frozen_bn(C, args.iters)
     if not only or "focal" in only:
