@@ -636,6 +636,29 @@ int detops_rpn_loss_backward_f32(float* const* grad_objectness_host, float* cons
                                  int N, int T, const float* upstream_objectness, const float* upstream_box,
                                  const float* inv_count, detops_stream_t stream);
 
+/* Sparse backward of the RPN head (modeling/rpn/rpn.py: t = relu(conv3x3(x) + b), objectness = 1x1(t), deltas = 1x1(t),
+ * one set of weights over every level) for a loss gradient that is zero except at a bounded number of anchors (the
+ * sampled RPN loss: <= N * BATCH_SIZE_PER_IMAGE rows).  Mathematically the dense backward — exact zeros contribute
+ * nothing — at the cost of the non-zero rows only; deterministic, no atomics on floating-point data, no host read-back.
+ *   grad_objectness[l] [N, A, H_l, W_l], grad_box_regression[l] [N, 4A, H_l, W_l]: the incoming gradients (fp32,
+ *   contiguous); x[l], t[l]: the head's input and hidden activation, CHANNELS-LAST [N, H_l, W_l, C]; grad_x[l]: same
+ *   layout, written in full (zero outside the 3x3 neighbourhoods of the non-zero rows).  HOST arrays of device pointers.
+ *   w_conv [C, 3, 3, C] (output channel, ky, kx, input channel: the channels-last storage of the [C, C, 3, 3] parameter),
+ *   w_cls [A, C], w_box [4A, C]; grad_w_conv / grad_w_cls / grad_w_box in the same layouts, grad_b_* [C] / [A] / [4A].
+ *   C must be a multiple of 4 (16-byte aligned rows); N * T and the batch's pixel count must stay below 2^31.
+ *   max_rows: static capacity of the row list.  A launch that finds MORE non-zero rows stays in bounds, fills
+ *   grad_w_conv with NaN (never a silently wrong step) and adds 1 to *overflow_count (device int32, never cleared by
+ *   the library, may be NULL).  workspace: detops_rpn_head_backward_workspace_bytes(N, T, max_rows, C) bytes,
+ *   T = A * sum_l H_l W_l. */
+size_t detops_rpn_head_backward_workspace_bytes(int N, int T, int max_rows, int C);
+int detops_rpn_head_backward_f32(const float* const* grad_objectness_host, const float* const* grad_box_regression_host,
+                                 const float* const* x_host, const float* const* t_host, float* const* grad_x_host,
+                                 const int* H_host, const int* W_host, int num_levels, int anchors_per_location, int N,
+                                 int C, int T, int max_rows, const float* w_conv, const float* w_cls, const float* w_box,
+                                 float* grad_w_conv, float* grad_b_conv, float* grad_w_cls, float* grad_b_cls,
+                                 float* grad_w_box, float* grad_b_box, int32_t* overflow_count, void* workspace,
+                                 size_t workspace_bytes, detops_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------
  * CPU branch — HOST pointers, no stream.  The reference `_C` serves exactly two operators for CPU tensors
  * (csrc/nms.h:19-27 -> csrc/cpu/nms_cpu.cpp, csrc/ROIAlign.h:19-24 -> csrc/cpu/ROIAlign_cpu.cpp) and raises

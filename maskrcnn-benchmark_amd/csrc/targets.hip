@@ -644,6 +644,346 @@ roi_head_targets_kernel(const float* __restrict__ boxes, const int64_t* __restri
   if (out_obj) out_obj[t] = objectness ? objectness[src] : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------ sparse RPN-head backward
+// The RPN loss evaluates <= BATCH_SIZE_PER_IMAGE sampled anchors per image, so d loss / d (objectness, deltas) is zero
+// except at <= R rows (R = 512 of 537,138 anchors at the headline shape).  The dense backward of the head
+// (t = relu(conv3x3(x) + b); objectness = 1x1(t); deltas = 1x1(t); shared over the levels) spends 2 x 211 GFLOP of
+// library convolutions on those zeros.  Here:
+//   head_rows_*      compact the non-zero anchor rows of every level, in the fixed order (level, image, y, x, anchor),
+//                    into a record list of static capacity with a device-side count (no host read-back);
+//   head_hidden      G[r, :] = relu'(t[pix_r, :]) * (g_o W_cls[a_r, :] + sum_k g_b[k] W_box[4 a_r + k, :]), a gathered copy
+//                    of t's rows and the addresses of the nine input rows under each row's 3x3 footprint;
+//   head_small       gradients of the two 1x1 convolutions and of the three biases (fixed-order sums over the rows);
+//   head_gemm<0>     D = G [R x C] . W_conv [C x 9C]      (per row: the gradient of its nine input pixels)
+//   head_gemm<1>     dW_conv = G^T [C x R] . X [R x 9C]   (X gathered through the row addresses; absent taps are zero)
+//   head_scatter     dX[q, :] = sum of the D slices aimed at pixel q, by ONE owner workgroup per pixel in list order.
+// Every launch is sized for the capacity and exits past the count.
+struct HeadLevels {
+  const float* gobj[DETOPS_MAX_LEVELS];
+  const float* gbox[DETOPS_MAX_LEVELS];
+  const float* x[DETOPS_MAX_LEVELS];
+  const float* t[DETOPS_MAX_LEVELS];
+  float* dx[DETOPS_MAX_LEVELS];
+  int H[DETOPS_MAX_LEVELS], W[DETOPS_MAX_LEVELS];
+  int first[DETOPS_MAX_LEVELS + 1];   // first anchor of the level in ONE image's list; first[num] = T
+  int pix0[DETOPS_MAX_LEVELS + 1];    // first pixel of the level in the batch's pixel list (N * the earlier planes)
+  int num;
+};
+
+struct HeadRow {
+  int key;      // pixel in the batch's pixel list: pix0[l] + (n * H + y) * W + x — the list is sorted by (key, a)
+  int l, n, y, x, a;
+  float g[5];   // gradient of the objectness logit and of the four deltas
+  int pad;
+};
+
+constexpr int kHeadItems = 4;   // candidate rows per thread of the compaction
+constexpr int kGemmT = 64, kGemmK = 16, kGemmLd = kGemmT + 4;
+
+// candidate j of [0, N * T): levels in order, inside a level (image, y, x, anchor)
+__device__ __forceinline__ bool head_row_at(const HeadLevels L, int A, int N, int64_t j, HeadRow& r) {
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < DETOPS_MAX_LEVELS; ++k)
+    if (k < L.num && j >= static_cast<int64_t>(N) * L.first[k]) l = k;
+  const float* gobj = L.gobj[0]; const float* gbox = L.gbox[0];
+  int H = L.H[0], W = L.W[0], first = L.first[0], pix0 = L.pix0[0];
+#pragma unroll
+  for (int k = 1; k < DETOPS_MAX_LEVELS; ++k)
+    if (k == l) { gobj = L.gobj[k]; gbox = L.gbox[k]; H = L.H[k]; W = L.W[k]; first = L.first[k]; pix0 = L.pix0[k]; }
+  const int plane = H * W;
+  const int rem = static_cast<int>(j - static_cast<int64_t>(N) * first);
+  const int n = rem / (plane * A), r2 = rem - n * plane * A;
+  const int loc = r2 / A, a = r2 - loc * A;
+  const size_t o1 = (static_cast<size_t>(n) * A + a) * plane + loc;
+  const size_t o4 = (static_cast<size_t>(n) * A + a) * 4 * plane + loc;
+  r.g[0] = gobj[o1];
+  bool nz = r.g[0] != 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    r.g[1 + k] = gbox[o4 + static_cast<size_t>(k) * plane];
+    nz = nz || r.g[1 + k] != 0.f;
+  }
+  r.l = l; r.n = n; r.y = loc / W; r.x = loc - r.y * W; r.a = a; r.pad = 0;
+  r.key = pix0 + n * plane + loc;
+  return nz;
+}
+
+// position of a flagged thread among the flagged threads of the workgroup, and their number
+__device__ __forceinline__ int head_block_rank(bool flag, int* wave_tot, int& total) {
+  const unsigned long long m = __ballot(flag);
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  const int rank = __popcll(m & ((1ull << lane) - 1ull));
+  __syncthreads();                       // the previous round's readers are done with wave_tot
+  if (lane == 0) wave_tot[w] = __popcll(m);
+  __syncthreads();
+  int before = 0;
+  total = 0;
+#pragma unroll
+  for (int k = 0; k < kBlock / kWave; ++k) {
+    if (k < w) before += wave_tot[k];
+    total += wave_tot[k];
+  }
+  return before + rank;
+}
+
+__global__ void __launch_bounds__(kBlock)
+head_rows_count_kernel(HeadLevels L, int A, int N, int64_t total, int* __restrict__ block_counts) {
+  __shared__ int wave_tot[kBlock / kWave];
+  int cnt = 0;
+  for (int it = 0; it < kHeadItems; ++it) {
+    const int64_t j = (static_cast<int64_t>(blockIdx.x) * kHeadItems + it) * kBlock + threadIdx.x;
+    HeadRow r;
+    const bool flag = j < total && head_row_at(L, A, N, j, r);
+    int tot;
+    head_block_rank(flag, wave_tot, tot);
+    cnt += tot;
+  }
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = cnt;
+}
+
+__global__ void __launch_bounds__(kBlock)
+head_rows_write_kernel(HeadLevels L, int A, int N, int64_t total, const int* __restrict__ block_counts, int max_rows,
+                       HeadRow* __restrict__ rows, int* __restrict__ count, int32_t* __restrict__ overflow) {
+  __shared__ int wave_tot[kBlock / kWave];
+  __shared__ int red[kBlock / kWave];
+  int before = 0;   // rows of the workgroups in front of this one
+  for (int b = threadIdx.x; b < static_cast<int>(blockIdx.x); b += kBlock) before += block_counts[b];
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) before += __shfl_down(before, off);
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = before;
+  __syncthreads();
+  int base = 0;
+#pragma unroll
+  for (int k = 0; k < kBlock / kWave; ++k) base += red[k];
+  for (int it = 0; it < kHeadItems; ++it) {
+    const int64_t j = (static_cast<int64_t>(blockIdx.x) * kHeadItems + it) * kBlock + threadIdx.x;
+    HeadRow r;
+    const bool flag = j < total && head_row_at(L, A, N, j, r);
+    int tot;
+    const int at = base + head_block_rank(flag, wave_tot, tot);
+    if (flag && at < max_rows) rows[at] = r;
+    base += tot;
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    count[0] = base;
+    if (base > max_rows && overflow) overflow[0] += 1;   // the only writer of the launch
+  }
+}
+
+// grid = max_rows: one workgroup per row
+__global__ void __launch_bounds__(kBlock)
+head_hidden_kernel(HeadLevels L, int C, const HeadRow* __restrict__ rows, const int* __restrict__ count, int max_rows,
+                   const float* __restrict__ w_cls, const float* __restrict__ w_box, float* __restrict__ G,
+                   float* __restrict__ Tm, const float** __restrict__ xrow) {
+  const int cnt = min(count[0], max_rows);
+  const int r = blockIdx.x;
+  if (r >= cnt) return;
+  const HeadRow R = rows[r];
+  const float* x = L.x[0]; const float* t = L.t[0];
+  int H = L.H[0], W = L.W[0];
+#pragma unroll
+  for (int k = 1; k < DETOPS_MAX_LEVELS; ++k)
+    if (k == R.l) { x = L.x[k]; t = L.t[k]; H = L.H[k]; W = L.W[k]; }
+  const size_t pix = (static_cast<size_t>(R.n) * H + R.y) * W + R.x;
+  const float* trow = t + pix * C;
+  const float* wc = w_cls + static_cast<size_t>(R.a) * C;
+  const float* wb = w_box + static_cast<size_t>(R.a) * 4 * C;
+  for (int c = threadIdx.x; c < C; c += kBlock) {
+    const float tv = trow[c];
+    float v = R.g[0] * wc[c];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v += R.g[1 + k] * wb[k * C + c];
+    G[static_cast<size_t>(r) * C + c] = (tv <= 0.f) ? 0.f : v;   // bias_act's ReLU rule: a NaN activation passes the gradient
+    Tm[static_cast<size_t>(r) * C + c] = tv;
+  }
+  if (threadIdx.x < 9) {
+    const int yy = R.y + static_cast<int>(threadIdx.x) / 3 - 1, xx = R.x + static_cast<int>(threadIdx.x) % 3 - 1;
+    const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+    xrow[r * 9 + threadIdx.x] = in ? x + ((static_cast<size_t>(R.n) * H + yy) * W + xx) * C : nullptr;
+  }
+}
+
+// grid = (5A + 1, ceil(C / 64)): output o < A: dW_cls[o, :], db_cls[o]; A <= o < 5A: dW_box[o - A, :], db_box[o - A];
+// o = 5A: db_conv.  A wave takes every fourth row; the four partial sums are added in wave order.
+__global__ void __launch_bounds__(kBlock)
+head_small_kernel(int A, int C, const HeadRow* __restrict__ rows, const int* __restrict__ count, int max_rows,
+                  const float* __restrict__ G, const float* __restrict__ Tm, float* __restrict__ gw_cls,
+                  float* __restrict__ gb_cls, float* __restrict__ gw_box, float* __restrict__ gb_box,
+                  float* __restrict__ gb_conv) {
+  __shared__ float red[kBlock / kWave][kWave];
+  __shared__ float redb[kBlock / kWave];
+  const int cnt = min(count[0], max_rows);
+  const int o = blockIdx.x;
+  const int lane = threadIdx.x & (kWave - 1), grp = threadIdx.x / kWave;
+  const int c = blockIdx.y * kWave + lane;
+  const bool conv = o == 5 * A;
+  const int a_o = o < A ? o : (o - A) / 4;
+  const int gi = o < A ? 0 : 1 + (o - A) % 4;
+  const float* src = conv ? G : Tm;
+  float acc = 0.f, accb = 0.f;
+  for (int r = grp; r < cnt; r += kBlock / kWave) {
+    float coef = 1.f;
+    if (!conv) {
+      if (rows[r].a != a_o) continue;
+      coef = rows[r].g[gi];
+    }
+    if (c < C) acc += coef * src[static_cast<size_t>(r) * C + c];
+    accb += coef;
+  }
+  red[grp][lane] = acc;
+  if (lane == 0) redb[grp] = accb;
+  __syncthreads();
+  if (grp != 0) return;
+  float v = 0.f, vb = 0.f;
+#pragma unroll
+  for (int k = 0; k < kBlock / kWave; ++k) { v += red[k][lane]; vb += redb[k]; }
+  if (c < C) {
+    if (conv) gb_conv[c] = v;
+    else if (o < A) gw_cls[static_cast<size_t>(o) * C + c] = v;
+    else gw_box[static_cast<size_t>(o - A) * C + c] = v;
+  }
+  if (lane == 0 && blockIdx.y == 0 && !conv) {
+    if (o < A) gb_cls[o] = vb; else gb_box[o - A] = vb;
+  }
+}
+
+// 64 x 64 output tile per workgroup, 4 x 4 per thread, 16-deep steps through LDS.
+//   MODE 0: out = D [rows x 9C] = G [rows x C] . w_conv [C x 9C]                  grid = (9C / 64, max_rows / 64)
+//   MODE 1: out = dW_conv [C x 9C] = G^T . X, X[r, tap * C + ci] = xrow[r * 9 + tap][ci] grid = (9C / 64, C / 64)
+//           (all NaN when the row list overflowed: the step's finite-loss check must see it)
+template <int MODE>
+__global__ void __launch_bounds__(kBlock)
+head_gemm_kernel(int C, const int* __restrict__ count, int max_rows, const float* __restrict__ G,
+                 const float* __restrict__ w_conv, const float* const* __restrict__ xrow, float* __restrict__ out) {
+  __shared__ float4 As4[kGemmK][kGemmLd / 4];   // (float4 storage: 16-byte aligned rows)
+  __shared__ float4 Bs4[kGemmK][kGemmLd / 4];
+  float (*As)[kGemmLd] = reinterpret_cast<float (*)[kGemmLd]>(As4);
+  float (*Bs)[kGemmLd] = reinterpret_cast<float (*)[kGemmLd]>(Bs4);
+  const int raw = count[0];
+  const int cnt = min(raw, max_rows);
+  const int NC = 9 * C;
+  const int M = MODE == 0 ? cnt : C, K = MODE == 0 ? C : cnt;
+  const int m0 = blockIdx.y * kGemmT, n0 = blockIdx.x * kGemmT;
+  if (m0 >= M) return;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int bk = tid >> 4, bc = (tid & 15) * 4, bn = n0 + bc;   // loader: row bk of the step, four columns from bc
+  const int tap = bn < NC ? bn / C : 0, ci = bn - tap * C;      // (C % 4 == 0: the four columns share a tap)
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  for (int k0 = 0; k0 < K; k0 += kGemmK) {
+    if (MODE == 0) {
+      const int m = m0 + (tid >> 2), kq = (tid & 3) * 4, k = k0 + kq;
+      float4 v = zero4;
+      if (m < M && k < K) v = *reinterpret_cast<const float4*>(G + static_cast<size_t>(m) * C + k);
+      As[kq + 0][tid >> 2] = v.x; As[kq + 1][tid >> 2] = v.y; As[kq + 2][tid >> 2] = v.z; As[kq + 3][tid >> 2] = v.w;
+    } else {
+      const int k = k0 + bk, m = m0 + bc;
+      float4 v = zero4;
+      if (k < K && m < M) v = *reinterpret_cast<const float4*>(G + static_cast<size_t>(k) * C + m);
+      *reinterpret_cast<float4*>(&As[bk][bc]) = v;
+    }
+    {
+      const int k = k0 + bk;
+      float4 v = zero4;
+      if (k < K && bn < NC) {
+        if (MODE == 0) {
+          v = *reinterpret_cast<const float4*>(w_conv + static_cast<size_t>(k) * NC + bn);
+        } else {
+          const float* p = xrow[k * 9 + tap];
+          if (p) v = *reinterpret_cast<const float4*>(p + ci);
+        }
+      }
+      *reinterpret_cast<float4*>(&Bs[bk][bc]) = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < kGemmK; ++kk) {
+      const float4 a = *reinterpret_cast<const float4*>(&As[kk][ty * 4]);
+      const float4 b = *reinterpret_cast<const float4*>(&Bs[kk][tx * 4]);
+      const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] += av[i] * bv[j];
+    }
+    __syncthreads();
+  }
+  const bool poison = MODE == 1 && raw > max_rows;
+  const float nan = __uint_as_float(0x7fc00000u);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + ty * 4 + i, n = n0 + tx * 4;
+    if (m < M && n < NC)
+      *reinterpret_cast<float4*>(out + static_cast<size_t>(m) * NC + n) =
+          poison ? make_float4(nan, nan, nan, nan) : make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+  }
+}
+
+__device__ __forceinline__ int head_lower_bound(const HeadRow* __restrict__ rows, int cnt, int key) {
+  int lo = 0, hi = cnt;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (rows[mid].key < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// grid = 9 * max_rows: workgroup (r, tap) aims at pixel q = pixel(r) + (ky - 1, kx - 1).  The contributions to q come from
+// the rows at the nine pixels q + (dy, dx) through tap (1 - dy, 1 - dx); the rows of a pixel are consecutive in the list.
+// The workgroup that holds the FIRST contribution in list order owns q and adds all of them in that order; the others leave.
+__global__ void __launch_bounds__(kWave)
+head_scatter_kernel(HeadLevels L, int C, const HeadRow* __restrict__ rows, const int* __restrict__ count, int max_rows,
+                    const float* __restrict__ D) {
+  const int cnt = min(count[0], max_rows);
+  const int r = blockIdx.x / 9, tap = blockIdx.x - r * 9;
+  if (r >= cnt) return;
+  const HeadRow R = rows[r];
+  float* dx = L.dx[0];
+  int H = L.H[0], W = L.W[0], pix0 = L.pix0[0];
+#pragma unroll
+  for (int k = 1; k < DETOPS_MAX_LEVELS; ++k)
+    if (k == R.l) { dx = L.dx[k]; H = L.H[k]; W = L.W[k]; pix0 = L.pix0[k]; }
+  const int qy = R.y + tap / 3 - 1, qx = R.x + tap % 3 - 1;
+  if (qy < 0 || qy >= H || qx < 0 || qx >= W) return;
+  const int qkey = R.key + (tap / 3 - 1) * W + (tap % 3 - 1);
+  int lo[9], hi[9];
+  bool owned = false;
+#pragma unroll
+  for (int nb = 0; nb < 9; ++nb) {
+    const int dy = nb / 3 - 1, dxx = nb % 3 - 1;
+    lo[nb] = hi[nb] = 0;
+    if (qy + dy < 0 || qy + dy >= H || qx + dxx < 0 || qx + dxx >= W) continue;
+    const int key = qkey + dy * W + dxx;
+    const int b = head_lower_bound(rows, cnt, key);
+    int e = b;
+    while (e < cnt && rows[e].key == key) ++e;
+    if (e == b) continue;
+    if (!owned) {
+      if (b != r || 8 - nb != tap) return;   // an earlier contribution exists: its workgroup owns q
+      owned = true;
+    }
+    lo[nb] = b; hi[nb] = e;
+  }
+  if (!owned) return;
+  const size_t NC = static_cast<size_t>(9) * C;
+  float* out = dx + static_cast<size_t>(qkey - pix0) * C;
+  for (int c = threadIdx.x * 4; c < C; c += kWave * 4) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int nb = 0; nb < 9; ++nb)
+      for (int rr = lo[nb]; rr < hi[nb]; ++rr) {
+        const float4 d = *reinterpret_cast<const float4*>(D + rr * NC + static_cast<size_t>(8 - nb) * C + c);
+        s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
+      }
+    *reinterpret_cast<float4*>(out + c) = s;
+  }
+}
+
 }  // namespace
 
 DETOPS_API size_t detops_match_boxes_workspace_bytes(int N, int M) {
@@ -843,5 +1183,101 @@ DETOPS_API int detops_rpn_loss_backward_f32(float* const* grad_objectness_host, 
   const int blocks = static_cast<int>(std::min<int64_t>(ceil_div64(static_cast<int64_t>(N) * T * 5, kBlock * 4), kRpnMaxBlocks));
   hipLaunchKernelGGL(rpn_loss_scale_kernel, dim3(std::max(blocks, 1)), dim3(kBlock), 0, as_stream(stream), L,
                      anchors_per_location, N, upstream_objectness, upstream_box, inv_count);
+  return launch_status();
+}
+
+namespace {
+struct HeadLayout {
+  size_t off_count, off_blocks, off_rows, off_xrow, off_G, off_T, off_D, total;
+  int nblocks;
+};
+
+HeadLayout head_layout(int N, int T, int max_rows, int C) {
+  HeadLayout l{};
+  const int64_t cand = static_cast<int64_t>(N) * T;
+  l.nblocks = static_cast<int>(std::max<int64_t>(ceil_div64(cand, static_cast<int64_t>(kBlock) * kHeadItems), 1));
+  const size_t R = static_cast<size_t>(max_rows);
+  size_t off = 0;
+  l.off_count = off;  off += 256;
+  l.off_blocks = off; off += up256(sizeof(int) * static_cast<size_t>(l.nblocks));
+  l.off_rows = off;   off += up256(sizeof(HeadRow) * R);
+  l.off_xrow = off;   off += up256(sizeof(const float*) * R * 9);
+  l.off_G = off;      off += up256(sizeof(float) * R * C);
+  l.off_T = off;      off += up256(sizeof(float) * R * C);
+  l.off_D = off;      off += up256(sizeof(float) * R * 9 * C);
+  l.total = off;
+  return l;
+}
+}  // namespace
+
+DETOPS_API size_t detops_rpn_head_backward_workspace_bytes(int N, int T, int max_rows, int C) {
+  if (N <= 0 || T <= 0 || max_rows <= 0 || C <= 0) return 256;
+  return head_layout(N, T, max_rows, C).total;
+}
+
+DETOPS_API int detops_rpn_head_backward_f32(const float* const* grad_objectness_host,
+                                            const float* const* grad_box_regression_host, const float* const* x_host,
+                                            const float* const* t_host, float* const* grad_x_host, const int* H_host,
+                                            const int* W_host, int num_levels, int anchors_per_location, int N, int C,
+                                            int T, int max_rows, const float* w_conv, const float* w_cls,
+                                            const float* w_box, float* grad_w_conv, float* grad_b_conv,
+                                            float* grad_w_cls, float* grad_b_cls, float* grad_w_box, float* grad_b_box,
+                                            int32_t* overflow_count, void* workspace, size_t workspace_bytes,
+                                            detops_stream_t stream) {
+  const int A = anchors_per_location;
+  if (num_levels < 1 || num_levels > DETOPS_MAX_LEVELS || A <= 0 || N <= 0 || C <= 0 || T <= 0 || max_rows <= 0)
+    return DETOPS_EINVAL;
+  if (!grad_objectness_host || !grad_box_regression_host || !x_host || !t_host || !grad_x_host || !H_host || !W_host ||
+      !w_conv || !w_cls || !w_box || !grad_w_conv || !grad_b_conv || !grad_w_cls || !grad_b_cls || !grad_w_box || !grad_b_box)
+    return DETOPS_EINVAL;
+  if (C % 4 != 0) return DETOPS_EUNSUPPORTED;
+  HeadLevels L{};
+  L.num = num_levels;
+  int64_t first = 0, pix = 0;
+  for (int l = 0; l < num_levels; ++l) {
+    if (H_host[l] <= 0 || W_host[l] <= 0 || !grad_objectness_host[l] || !grad_box_regression_host[l] || !x_host[l] ||
+        !t_host[l] || !grad_x_host[l])
+      return DETOPS_EINVAL;
+    L.gobj[l] = grad_objectness_host[l]; L.gbox[l] = grad_box_regression_host[l];
+    L.x[l] = x_host[l]; L.t[l] = t_host[l]; L.dx[l] = grad_x_host[l];
+    L.H[l] = H_host[l]; L.W[l] = W_host[l];
+    L.first[l] = static_cast<int>(first);
+    L.pix0[l] = static_cast<int>(pix);
+    first += static_cast<int64_t>(H_host[l]) * W_host[l] * A;
+    pix += static_cast<int64_t>(N) * H_host[l] * W_host[l];
+  }
+  if (first != T) return DETOPS_EINVAL;   // the anchor list must be exactly the concatenation of the level grids
+  if (static_cast<int64_t>(N) * T >= (int64_t{1} << 31) || pix >= (int64_t{1} << 31) ||
+      static_cast<int64_t>(max_rows) * 9 * C >= (int64_t{1} << 31))
+    return DETOPS_EUNSUPPORTED;
+  for (int l = num_levels; l <= DETOPS_MAX_LEVELS; ++l) { L.first[l] = T; L.pix0[l] = static_cast<int>(pix); }
+  const HeadLayout lay = head_layout(N, T, max_rows, C);
+  if (!workspace || workspace_bytes < lay.total) return DETOPS_EWORKSPACE;
+  unsigned char* base = static_cast<unsigned char*>(workspace);
+  int* count = reinterpret_cast<int*>(base + lay.off_count);
+  int* block_counts = reinterpret_cast<int*>(base + lay.off_blocks);
+  HeadRow* rows = reinterpret_cast<HeadRow*>(base + lay.off_rows);
+  const float** xrow = reinterpret_cast<const float**>(base + lay.off_xrow);
+  float* G = reinterpret_cast<float*>(base + lay.off_G);
+  float* Tm = reinterpret_cast<float*>(base + lay.off_T);
+  float* D = reinterpret_cast<float*>(base + lay.off_D);
+  hipStream_t st = as_stream(stream);
+  const int64_t cand = static_cast<int64_t>(N) * T;
+  for (int l = 0; l < num_levels; ++l)
+    DETOPS_HIP_TRY(hipMemsetAsync(L.dx[l], 0, sizeof(float) * static_cast<size_t>(N) * L.H[l] * L.W[l] * C, st));
+  hipLaunchKernelGGL(head_rows_count_kernel, dim3(lay.nblocks), dim3(kBlock), 0, st, L, A, N, cand, block_counts);
+  hipLaunchKernelGGL(head_rows_write_kernel, dim3(lay.nblocks), dim3(kBlock), 0, st, L, A, N, cand, block_counts, max_rows,
+                     rows, count, overflow_count);
+  hipLaunchKernelGGL(head_hidden_kernel, dim3(max_rows), dim3(kBlock), 0, st, L, C, rows, count, max_rows, w_cls, w_box, G,
+                     Tm, xrow);
+  hipLaunchKernelGGL(head_small_kernel, dim3(5 * A + 1, static_cast<unsigned>(ceil_div64(C, kWave))), dim3(kBlock), 0, st,
+                     A, C, rows, count, max_rows, G, Tm, grad_w_cls, grad_b_cls, grad_w_box, grad_b_box, grad_b_conv);
+  const unsigned nt = static_cast<unsigned>(ceil_div64(static_cast<int64_t>(9) * C, kGemmT));
+  hipLaunchKernelGGL(head_gemm_kernel<1>, dim3(nt, static_cast<unsigned>(ceil_div64(C, kGemmT))), dim3(kBlock), 0, st, C,
+                     count, max_rows, G, w_conv, xrow, grad_w_conv);
+  hipLaunchKernelGGL(head_gemm_kernel<0>, dim3(nt, static_cast<unsigned>(ceil_div64(max_rows, kGemmT))), dim3(kBlock), 0,
+                     st, C, count, max_rows, G, w_conv, xrow, D);
+  hipLaunchKernelGGL(head_scatter_kernel, dim3(static_cast<unsigned>(max_rows) * 9), dim3(kWave), 0, st, L, C, rows, count,
+                     max_rows, D);
   return launch_status();
 }

@@ -1340,6 +1340,19 @@ def bias_act_supported(x, bias):
             and is_channels_last(x))
 
 
+def _bias_act_forward(x, bias, relu):
+    """-> ([relu](x + bias[c]), served by the fused kernel?) — `x` may be overwritten"""
+    fused = bool(lib.detops_bias_act_supported(int(x.shape[1])))
+    if fused:
+        y = frozen_bn_act_forward(x, _ones(x.shape[1], x.device), bias.contiguous(), None, relu)
+    else:
+        bb = bias.to(x.dtype).view(1, -1, 1, 1)
+        y = x.add_(bb) if not x.requires_grad else x + bb
+        if relu:
+            y = y.relu_()
+    return y, fused
+
+
 class _BiasAct(torch.autograd.Function):
     """y = [relu](x + bias[c]) on a channels-last activation (csrc/bias_act.hip).  The point is the BACKWARD: the bias
     gradient of a channels-last gradient is a column sum over [N*H*W, C]; PyTorch's `sum((0, 2, 3))` runs it through a generic
@@ -1347,14 +1360,7 @@ class _BiasAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, relu):
-        ctx.fused = bool(lib.detops_bias_act_supported(int(x.shape[1])))
-        if ctx.fused:
-            y = frozen_bn_act_forward(x, _ones(x.shape[1], x.device), bias.contiguous(), None, relu)
-        else:
-            bb = bias.to(x.dtype).view(1, -1, 1, 1)
-            y = x.add_(bb) if not x.requires_grad else x + bb
-            if relu:
-                y = y.relu_()
+        y, ctx.fused = _bias_act_forward(x, bias, relu)
         ctx.relu = relu
         ctx.save_for_backward(y if relu else None)
         return y
@@ -1400,6 +1406,125 @@ def bias_act(x, bias, relu=False):
     (it is the caller's fresh convolution output)."""
     _need_cuda("bias_act", x, bias)
     return _BiasAct.apply(x, bias, bool(relu))
+
+
+# ------------------------------------------------------------------------------------------ sparse RPN-head backward
+_RPN_SPARSE_STATUS = {}
+
+
+def rpn_sparse_status(device):
+    """The sticky device word (int32 [1]) of the sparse RPN-head backward: incremented by every backward that found more
+    non-zero gradient rows than its static capacity (that step's conv-weight gradient is NaN).  One per device, never
+    cleared by the library, never read by the launch path."""
+    device = torch.device(device)
+    key = (device.type, device.index if device.index is not None else (torch.cuda.current_device() if device.type == "cuda" else 0))
+    t = _RPN_SPARSE_STATUS.get(key)
+    if t is None:
+        t = _RPN_SPARSE_STATUS[key] = torch.zeros((1,), dtype=torch.int32, device=device)
+    return t
+
+
+def rpn_sparse_overflows(device=None, reset=False):
+    """Host-side read of the status words (a device->host copy: call it where a read-back happens anyway).  Returns the
+    number of sparse RPN-head backward passes whose row list overflowed since the last reset."""
+    total = 0
+    for (typ, idx), t in list(_RPN_SPARSE_STATUS.items()):
+        if device is not None and torch.device(device).type != typ:
+            continue
+        total += int(t.item())
+        if reset:
+            t.zero_()
+    return total
+
+
+def _conv_bias_act_plain(x, weight, bias, padding, relu):
+    """layers.misc.conv_bias_act's channels-last branch without autograd: bias-free convolution, then the bias (+ ReLU) pass"""
+    y = torch.nn.functional.conv2d(x, weight, None, 1, padding)
+    if bias_act_supported(y, bias):
+        return _bias_act_forward(y, bias, relu)[0]
+    y = y + bias.to(y.dtype).view(1, -1, 1, 1)
+    return torch.relu(y) if relu else y
+
+
+class _RpnHeadSparse(torch.autograd.Function):
+    """The whole RPN head (shared 3x3 conv + ReLU, 1x1 objectness, 1x1 box deltas) over every level as ONE node whose
+    backward touches only the anchors that carry gradient (csrc/targets.hip, "sparse RPN-head backward").  The forward is
+    the dense head's; `max_rows` bounds the non-zero rows of the incoming gradients (see modeling/rpn/rpn.py)."""
+
+    @staticmethod
+    def forward(ctx, max_rows, w_conv, b_conv, w_cls, b_cls, w_box, b_box, *features):
+        xs, ts, obj, box = [], [], [], []
+        for x in features:
+            x = x.contiguous(memory_format=torch.channels_last)
+            t = _conv_bias_act_plain(x, w_conv, b_conv, 1, True).contiguous(memory_format=torch.channels_last)
+            obj.append(_conv_bias_act_plain(t, w_cls, b_cls, 0, False).contiguous())
+            box.append(_conv_bias_act_plain(t, w_box, b_box, 0, False).contiguous())
+            xs.append(x)
+            ts.append(t)
+        ctx.max_rows, ctx.levels = int(max_rows), len(features)
+        ctx.save_for_backward(w_conv, w_cls, w_box, *(xs + ts))
+        return tuple(obj + box)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        L, R = ctx.levels, ctx.max_rows
+        w_conv, w_cls, w_box = ctx.saved_tensors[:3]
+        xs, ts = ctx.saved_tensors[3:3 + L], ctx.saved_tensors[3 + L:]
+        N, C = int(xs[0].shape[0]), int(xs[0].shape[1])
+        A = int(w_cls.shape[0])
+        dev = xs[0].device
+        gobj = [(g.float().contiguous() if g is not None else torch.zeros((N, A) + tuple(x.shape[2:]), device=dev))
+                for g, x in zip(grads[:L], xs)]
+        gbox = [(g.float().contiguous() if g is not None else torch.zeros((N, 4 * A) + tuple(x.shape[2:]), device=dev))
+                for g, x in zip(grads[L:], xs)]
+        Hs = (ctypes.c_int * L)(*[int(x.shape[2]) for x in xs])
+        Ws = (ctypes.c_int * L)(*[int(x.shape[3]) for x in xs])
+        T = A * sum(int(x.shape[2]) * int(x.shape[3]) for x in xs)
+        # the kernels read the 3x3 weight as [C_out, ky, kx, C_in] — the channels-last parameter's own storage (no copy)
+        wk = w_conv.permute(0, 2, 3, 1).contiguous()
+        wc = w_cls.reshape(A, C).contiguous()
+        wb = w_box.reshape(4 * A, C).contiguous()
+        gwk = torch.empty((C, 3, 3, C), dtype=torch.float32, device=dev)
+        gb_conv = torch.empty((C,), dtype=torch.float32, device=dev)
+        gw_cls = torch.empty((A, C), dtype=torch.float32, device=dev)
+        gb_cls = torch.empty((A,), dtype=torch.float32, device=dev)
+        gw_box = torch.empty((4 * A, C), dtype=torch.float32, device=dev)
+        gb_box = torch.empty((4 * A,), dtype=torch.float32, device=dev)
+        dxs = [torch.empty_like(x) for x in xs]
+        nbytes = int(lib.detops_rpn_head_backward_workspace_bytes(N, T, R, C))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        arr = lambda tensors: (ctypes.c_void_p * L)(*[t.data_ptr() for t in tensors])
+        with _on_device(xs[0]), _timed(("rpn_head_bwd[N=%d,R=%d,C=%d]", (N, R, C)), xs[0]):
+            check(lib.detops_rpn_head_backward_f32(arr(gobj), arr(gbox), arr(xs), arr(ts), arr(dxs), Hs, Ws, L, A, N, C, T, R,
+                                                   ptr(wk), ptr(wc), ptr(wb), ptr(gwk), ptr(gb_conv), ptr(gw_cls), ptr(gb_cls),
+                                                   ptr(gw_box), ptr(gb_box), ptr(rpn_sparse_status(dev)), ptr(ws), nbytes,
+                                                   stream_of(xs[0])), "rpn_head_backward")
+        # each weight gradient in its parameter's memory format (the data-parallel bucket views carry those strides)
+        gw_conv = gwk.permute(0, 3, 1, 2)
+        if w_conv.is_contiguous():
+            gw_conv = gw_conv.contiguous()
+        need = ctx.needs_input_grad
+        return (None, gw_conv, gb_conv, gw_cls.view(w_cls.shape), gb_cls, gw_box.view(w_box.shape), gb_box) + tuple(
+            d if need[7 + i] else None for i, d in enumerate(dxs))
+
+
+def rpn_head_sparse_supported(features, params):
+    """fp32 channels-last features and fp32 parameters on the device, C a multiple of 4 (the kernels' 16-byte rows)"""
+    return (all(on_device(t) and t.dtype == torch.float32 for t in list(features) + list(params))
+            and all(f.dim() == 4 and f.numel() > 0 and is_channels_last(f) for f in features)
+            and int(features[0].shape[1]) % 4 == 0 and 0 < len(features) <= 8)
+
+
+def rpn_head_sparse(features, w_conv, b_conv, w_cls, b_cls, w_box, b_box, max_rows):
+    """(objectness per level [N, A, H, W], box deltas per level [N, 4A, H, W]) of the RPN head with the sparse backward
+    (extension).  `max_rows` >= the number of anchors of the batch whose loss gradient is non-zero."""
+    params = (w_conv, b_conv, w_cls, b_cls, w_box, b_box)
+    _need_cuda("rpn_head_sparse", *(list(features) + list(params)))
+    if not rpn_head_sparse_supported(features, params):
+        raise RuntimeError("rpn_head_sparse: fp32 channels-last features and fp32 parameters are required")
+    out = _RpnHeadSparse.apply(int(max_rows), *params, *features)
+    L = len(features)
+    return list(out[:L]), list(out[L:])
 
 
 # ------------------------------------------------------------------------------------------ deformable conv

@@ -41,6 +41,8 @@ SIGNATURES = {
     "detops_rpn_loss_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float,
                                     _P, _P, _P, _P, _P, c_size_t, _P]),
     "detops_rpn_loss_backward_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "detops_rpn_head_backward_workspace_bytes": (c_size_t, [c_int] * 4),
+    "detops_rpn_head_backward_f32": (c_int, [_P] * 7 + [c_int] * 6 + [_P] * 10 + [_P, c_size_t, _P]),
     "detops_roi_align_forward_cpu_f32": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int]),
     "detops_roi_align_forward_ws_f32": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int, _P, c_size_t, _P]),
     "detops_roi_align_fpn_forward_ws_f32": (

@@ -1,4 +1,6 @@
 """RPN head + module (reference modeling/rpn/rpn.py:14-208)."""
+import os
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -10,7 +12,14 @@ from maskrcnn_benchmark.modeling.box_coder import BoxCoder
 
 from .anchor_generator import make_anchor_generator
 from .inference import make_rpn_postprocessor
-from .loss import make_rpn_loss_evaluator
+from .loss import RPNLossComputation, make_rpn_loss_evaluator
+
+# A/B switch of the sparse RPN-head backward: "0" the dense library backward (the previous behaviour), "1" (default) sparse
+# where the static shape test says it pays, "force" sparse wherever the kernels serve the tensors (tests)
+_SPARSE_BWD = os.environ.get("DETOPS_RPN_SPARSE_BWD", "1")
+# The dense backward costs ~4 * 9 C^2 FLOP per pyramid pixel at the library's matrix-core rate, the sparse one the same per
+# gradient ROW on plain FMA kernels an order of magnitude below that rate: it pays while rows * 16 <= pixels.
+_SPARSE_PIXELS_PER_ROW = 16
 
 
 class RPNHeadConvRegressor(nn.Module):
@@ -42,7 +51,26 @@ class RPNHead(nn.Module):
             nn.init.normal_(m.weight, std=0.01)
             nn.init.constant_(m.bias, 0)
 
-    def forward(self, x):
+    def _sparse_ok(self, x, rows):
+        if _SPARSE_BWD == "0" or not rows or not torch.is_grad_enabled() or torch.is_autocast_enabled():
+            return False
+        from maskrcnn_benchmark import _C
+        # (the weights are read here, at forward time: HalfWeights swaps `module.weight` per step)
+        params = (self.conv.weight, self.conv.bias, self.cls_logits.weight, self.cls_logits.bias, self.bbox_pred.weight,
+                  self.bbox_pred.bias)
+        if len(x) == 0 or not all(torch.is_tensor(p) for p in params) or not _C.rpn_head_sparse_supported(x, params):
+            return False
+        pixels = sum(int(f.shape[0]) * int(f.shape[2]) * int(f.shape[3]) for f in x)
+        return _SPARSE_BWD == "force" or rows * _SPARSE_PIXELS_PER_ROW <= pixels
+
+    def forward(self, x, sparse_rows=None):
+        """`sparse_rows`: the caller's promise that at most this many anchors of the batch receive a non-zero gradient (the
+        sampled RPN loss): the head then runs as one autograd node with the sparse backward where that pays.  Default:
+        the dense per-level composition."""
+        if sparse_rows is not None and self._sparse_ok(x, sparse_rows):
+            from maskrcnn_benchmark import _C
+            return _C.rpn_head_sparse(list(x), self.conv.weight, self.conv.bias, self.cls_logits.weight, self.cls_logits.bias,
+                                      self.bbox_pred.weight, self.bbox_pred.bias, sparse_rows)
         logits, bbox_reg = [], []
         for feature in x:
             t = conv_bias_act(self.conv, feature, relu=True)      # channels-last: conv, then ONE fused bias + ReLU pass
@@ -69,8 +97,19 @@ class RPNModule(nn.Module):
         self.box_selector_test = make_rpn_postprocessor(cfg, rpn_box_coder, is_train=False)
         self.loss_evaluator = make_rpn_loss_evaluator(cfg, rpn_box_coder)
 
+    def _sparse_rows(self, features):
+        """Upper bound on the anchors of the batch with a non-zero loss gradient, or None when there is no such bound: the
+        sampled RPN loss evaluates <= BATCH_SIZE_PER_IMAGE anchors per image and nothing else backpropagates into the head
+        (the proposals are taken under no_grad)."""
+        if type(self.loss_evaluator) is not RPNLossComputation or type(self.head) is not RPNHead or len(features) == 0:
+            return None
+        A = self.anchor_generator.num_anchors_per_location()[0]
+        per_image = A * sum(int(f.shape[2]) * int(f.shape[3]) for f in features)
+        return int(features[0].shape[0]) * min(int(self.loss_evaluator.fg_bg_sampler.batch_size_per_image), per_image)
+
     def forward(self, images, features, targets=None):
-        objectness, rpn_box_regression = self.head(features)
+        rows = self._sparse_rows(features) if self.training and targets is not None else None
+        objectness, rpn_box_regression = self.head(features) if rows is None else self.head(features, sparse_rows=rows)
         anchors = self.anchor_generator(images, features)
         if self.training:
             return self._forward_train(anchors, objectness, rpn_box_regression, targets)
