@@ -1589,10 +1589,6 @@ def _shape_check(input, offset, grad_output, weight, kH, kW, dH, dW, padH, padW,
     return Ho, Wo
 
 
-def _geom_args(B, C, H, W, kH, kW, padH, padW, dH, dW, dilH, dilW, dg):
-    return (B, C, H, W, kH, kW, padH, padW, dH, dW, dilH, dilW, dg)
-
-
 def deformable_im2col(im, offset, mask, kH, kW, padH, padW, dH, dW, dilH, dilW, dg):
     """col [C*kH*kW, B*Ho*Wo] (deform_conv_kernel_cuda.cu:197-250 / :577-640)."""
     code = _dcn_check("deformable_im2col", im, offset, mask)
@@ -1600,9 +1596,8 @@ def deformable_im2col(im, offset, mask, kH, kW, padH, padW, dH, dW, dilH, dilW, 
     Ho, Wo = _out_hw(H, W, kH, kW, padH, padW, dH, dW, dilH, dilW)
     col = torch.empty((C * kH * kW, B * Ho * Wo), dtype=im.dtype, device=im.device)
     with _on_device(im), _timed(("dcn_im2col[B=%d,C=%d,%dx%d,k=%d,e=%d,m=%d]", (B, C, H, W, kH, _ESIZE[im.dtype], mask is not None)), im, every=8):
-        check(lib.detops_deformable_im2col(ptr(im), ptr(offset), ptr(mask), ptr(col), code,
-                                           *_geom_args(B, C, H, W, kH, kW, padH, padW, dH, dW, dilH,
-                                                       dilW, dg), stream_of(im)), "deformable_im2col")
+        check(lib.detops_deformable_im2col(ptr(im), ptr(offset), ptr(mask), ptr(col), code, B, C, H, W, kH, kW, padH, padW,
+                                           dH, dW, dilH, dilW, dg, stream_of(im)), "deformable_im2col")
     return col
 
 
@@ -1610,7 +1605,7 @@ def deformable_col2im(col, offset, mask, grad_im, kH, kW, padH, padW, dH, dW, di
     """accumulates into grad_im [B,C,H,W] (deform_conv_kernel_cuda.cu:286-342 / :642-700)."""
     code = _dcn_check("deformable_col2im", col, offset, mask, grad_im)
     B, C, H, W = grad_im.shape
-    geom = _geom_args(B, C, H, W, kH, kW, padH, padW, dH, dW, dilH, dilW, dg)
+    geom = (B, C, H, W, kH, kW, padH, padW, dH, dW, dilH, dilW, dg)
     with _on_device(col):
         # gather lists for the atomic-free path live in a scratch tensor (torch's caching allocator:
         # stream-ordered reuse, no hipMalloc per call); 0 bytes = shape outside the index plan
@@ -1628,10 +1623,8 @@ def deformable_col2im_coord(col, im, offset, mask, grad_offset, grad_mask, kH, k
     B, C, H, W = im.shape
     with _on_device(col), _timed(("dcn_col2im_coord[B=%d,C=%d,%dx%d,k=%d,e=%d,m=%d]", (B, C, H, W, kH, _ESIZE[col.dtype], mask is not None)), col, every=8):
         check(lib.detops_deformable_col2im_coord(ptr(col), ptr(im), ptr(offset), ptr(mask),
-                                                 ptr(grad_offset), ptr(grad_mask), code,
-                                                 *_geom_args(B, C, H, W, kH, kW, padH, padW, dH, dW,
-                                                             dilH, dilW, dg), stream_of(col)),
-              "deformable_col2im_coord")
+                                                 ptr(grad_offset), ptr(grad_mask), code, B, C, H, W, kH, kW, padH, padW,
+                                                 dH, dW, dilH, dilW, dg, stream_of(col)), "deformable_col2im_coord")
 
 
 def _fused_dcn_forward(input, weight, offset, mask, bias, out, kH, kW, padH, padW, dH, dW, dilH, dilW, group, dg):
@@ -1773,44 +1766,70 @@ def _nhwc_forward(input, weight, offset, mask, bias, out, geom):
     return xT, colT
 
 
-def _nhwc_backward(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
-                   geom, scale=1.0):
-    """any of grad_input+grad_offset(+grad_mask) / grad_weight(+grad_bias) may be None (the v1 entry points ask for
-    them in two separate calls); accumulate / overwrite semantics of the reference functions"""
-    B, C, H, W = input.shape
-    Cout = weight.size(0) if weight is not None else grad_weight.size(0)
-    xT = _to_nhwc(input)
-    gT = _to_nhwc(grad_output)                                   # [B, Ho*Wo, Cout]
+def _w_cin_major(weight):
+    """[Cout, C, kh, kw] -> W2T [C, kh*kw*Cout] (the column order of S_T)"""
+    return weight.permute(1, 2, 3, 0).reshape(weight.size(1), -1)
+
+
+def _nhwc_backward_core(xT, colT, gT, weight, offset, mask, B, C, H, W, geom, need_input, need_weight, need_bias,
+                        grad_offset=None, grad_mask=None):
+    """The channels-last backward pass that deform_conv_backward_all (the layers) and the reference-named entry points both
+    run; each adds only its final layout step.  `xT` [B, H*W, C] / `gT` [B, Ho*Wo, Cout]: channel-fastest input and output
+    gradient; `colT`: the forward's kept column matrix, or None (rebuilt for the weight gradient); `grad_offset` /
+    `grad_mask`: the caller's buffers, or None (fresh ones).  -> (ginT, S_T, grad_offset, grad_mask, gw2, grad_bias), None where
+    not asked for: the input gradient is `ginT` [B, H*W, C], or (DCN_INPUT_GRAD == "transposed", shapes outside the gather's
+    plan) `S_T` [B*H*W, kh*kw*Cout] for the caller to multiply with _w_cin_major(weight); `gw2` is [Cout, kh*kw*C]."""
+    Cout = gT.size(2)
     g2 = gT.view(-1, Cout)
-    if grad_input is not None:
-        W2 = _w_tap_major(weight)                                # [Cout, K*C]
-        colsG = torch.mm(g2, W2)                                 # column gradient, channel-fastest: [B*Ho*Wo, K*C]
+    ginT = S_T = gw2 = grad_bias = None
+    if need_input:
+        colsG = torch.mm(g2, _w_tap_major(weight))               # column gradient, channel-fastest: [B*Ho*Wo, K*C]
+        if grad_offset is None:
+            grad_offset = torch.empty_like(offset)               # written in full by the coordinate kernel
+            grad_mask = torch.empty_like(mask) if mask is not None else None
         _coord_nhwc(colsG, xT, offset, mask, grad_offset, grad_mask, B, C, H, W, geom)
+        # input gradient: col2im of the column gradient as a gather (no S_T, no second conv-sized GEMM); the transposed
+        # sampling of the output gradient + GEMM of rounds 3-5 stays as the A/B form and for shapes outside the gather's plan
         ginT = _col2im_nhwc(colsG, offset, mask, B, C, H, W, geom) if DCN_INPUT_GRAD == "col2im" else None
         del colsG
-        if ginT is not None:       # [B, H*W, C]: accumulated into the caller's (reference semantics) NCHW gradient
-            grad_input.view(B, C, -1).add_(ginT.transpose(1, 2))
-        else:
+        if ginT is None:
             S_T = _transposed_sample(gT, offset, mask, B, C, H, W, Cout, geom)     # [B*H*W, K*Cout]
-            W2T = weight.permute(1, 2, 3, 0).reshape(C, -1)          # [C, K*Cout]
-            grad_input.view(B, C, -1).baddbmm_(W2T.unsqueeze(0).expand(B, -1, -1), S_T.view(B, H * W, -1).transpose(1, 2))
-    if grad_weight is not None:
-        colT = _im2col_nhwc(xT, offset, mask, B, C, H, W, geom)  # [B*Ho*Wo, K*C]
-        gw2 = torch.mm(g2.t(), colT)                             # [Cout, K*C]
-        kH, kW = geom[0], geom[1]
-        grad_weight.add_(gw2.view(Cout, kH, kW, C).permute(0, 3, 1, 2), alpha=float(scale))
-        if grad_bias is not None:
-            grad_bias += g2.sum(0)
+    if need_weight:
+        if colT is None:
+            colT = _im2col_nhwc(xT, offset, mask, B, C, H, W, geom)  # [B*Ho*Wo, K*C]
+        gw2 = torch.mm(g2.t(), colT)
+    if need_bias:
+        grad_bias = g2.sum(0)
+    return ginT, S_T, grad_offset, grad_mask, gw2, grad_bias
+
+
+def _nhwc_backward(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
+                   geom, scale=1.0):
+    """the reference-named backward entry points on the channels-last plan: accumulates into grad_input / grad_weight /
+    grad_bias, the coordinate kernel overwrites grad_offset / grad_mask in place.  Either half (input+offset(+mask) /
+    weight(+bias)) may be None: the v1 entry points ask for them in two calls."""
+    B, C, H, W = input.shape
+    ginT, S_T, _, _, gw2, gb = _nhwc_backward_core(
+        _to_nhwc(input), None, _to_nhwc(grad_output), weight, offset, mask, B, C, H, W, geom, grad_input is not None,
+        grad_weight is not None, grad_weight is not None and grad_bias is not None, grad_offset, grad_mask)
+    if ginT is not None:       # [B, H*W, C]: accumulated into the caller's NCHW gradient
+        grad_input.view(B, C, -1).add_(ginT.transpose(1, 2))
+    elif S_T is not None:
+        grad_input.view(B, C, -1).baddbmm_(_w_cin_major(weight).unsqueeze(0).expand(B, -1, -1), S_T.view(B, H * W, -1).transpose(1, 2))
+    if gw2 is not None:
+        grad_weight.add_(gw2.view(-1, geom[0], geom[1], C).permute(0, 3, 1, 2), alpha=float(scale))
+    if gb is not None:
+        grad_bias += gb
 
 
 def deform_conv_backward_all(input, offset, mask, weight, grad_output, kH, kW, padH, padW, dH, dW, dilH, dilW, group,
                              deformable_group, need_input=True, need_weight=True, need_bias=False, saved=None):
     """Extension (not a name of the reference's `_C`): every gradient of one deformable convolution (v1: mask None;
     v2: modulated) from ONE pass over the channels-last pipeline.  The reference API (deform_conv_backward_input +
-    deform_conv_backward_parameters, kept above) asks for them in two calls, each of which must rebuild the
-    channel-fastest copies of the input and of the output gradient and accumulates into caller-zeroed tensors:
-    per layer that is two extra transposes, three fills and an accumulate — about a third of the launches of a
-    host-bound step (R-101 + DCN under fp16).
+    deform_conv_backward_parameters, below: the same _nhwc_backward_core) asks for them in two calls, each of which must
+    rebuild the channel-fastest copies of the input and of the output gradient and accumulates into caller-zeroed tensors:
+    per layer that is two extra transposes, three fills and an accumulate — about a third of the launches of a host-bound
+    step (R-101 + DCN under fp16).
 
     `saved` = what the forward pass of the same layer kept (`keep=[]` of deform_conv_forward /
     modulated_deform_conv_forward: the channel-fastest input copy and the column matrix): neither is rebuilt then
@@ -1829,43 +1848,28 @@ def deform_conv_backward_all(input, offset, mask, weight, grad_output, kH, kW, p
     if mask is not None:
         mask = mask.contiguous()
     B, C, H, W = input.shape
-    Cout = weight.size(0)
     xT, colT = saved if saved is not None else (_to_nhwc(input), None)
-    gT = _to_nhwc(grad_output)                                   # [B, Ho*Wo, Cout]
-    g2 = gT.view(-1, Cout)
-    grad_input = grad_offset = grad_mask = grad_weight = grad_bias = None
-    if need_input:
-        colsG = torch.mm(g2, _w_tap_major(weight))               # column gradient, channel-fastest: [B*Ho*Wo, K*C]
-        grad_offset = torch.empty_like(offset)                   # written in full by the coordinate kernel
-        grad_mask = torch.empty_like(mask) if mask is not None else None
-        _coord_nhwc(colsG, xT, offset, mask, grad_offset, grad_mask, B, C, H, W, geom)
-        # input gradient: col2im of the column gradient as a gather (no S_T, no second conv-sized GEMM); the transposed
-        # sampling of the output gradient + GEMM of rounds 3-5 stays as the A/B form and for shapes outside the gather's plan
-        ginT = _col2im_nhwc(colsG, offset, mask, B, C, H, W, geom) if DCN_INPUT_GRAD == "col2im" else None
-        del colsG
-        if ginT is not None:
-            if cl_in:  # the input was channels-last: so is its gradient ([B, H*W, C] viewed as [B, C, H, W])
-                grad_input = ginT.view(B, H, W, C).permute(0, 3, 1, 2)
-            else:      # [B, H*W, C] -> [B, C, H*W]: the same tile transpose with the roles of C and H*W swapped
-                grad_input = torch.empty((B, C, H, W), dtype=ginT.dtype, device=ginT.device)
-                with _on_device(ginT):
-                    check(lib.detops_nchw_to_nhwc(ptr(ginT), ptr(grad_input), _lib.DTYPE_CODE[ginT.dtype], B, H * W, C,
-                                                  stream_of(ginT)), "nhwc_to_nchw")
+    ginT, S_T, grad_offset, grad_mask, grad_weight, grad_bias = _nhwc_backward_core(
+        xT, colT, _to_nhwc(grad_output), weight, offset, mask, B, C, H, W, geom, need_input, need_weight, need_bias)
+    grad_input = None
+    if ginT is not None:
+        if cl_in:  # the input was channels-last: so is its gradient ([B, H*W, C] viewed as [B, C, H, W])
+            grad_input = ginT.view(B, H, W, C).permute(0, 3, 1, 2)
+        else:      # [B, H*W, C] -> [B, C, H*W]: the same tile transpose with the roles of C and H*W swapped
+            grad_input = torch.empty((B, C, H, W), dtype=ginT.dtype, device=ginT.device)
+            with _on_device(ginT):
+                check(lib.detops_nchw_to_nhwc(ptr(ginT), ptr(grad_input), _lib.DTYPE_CODE[ginT.dtype], B, H * W, C,
+                                              stream_of(ginT)), "nhwc_to_nchw")
+    elif S_T is not None:
+        W2T = _w_cin_major(weight)                               # [C, K*Cout]
+        if cl_in:     # the input was channels-last: so is its gradient ([B*H*W, C] from one GEMM, viewed as [B, C, H, W])
+            grad_input = torch.mm(S_T, W2T.t()).view(B, H, W, C).permute(0, 3, 1, 2)
         else:
-            S_T = _transposed_sample(gT, offset, mask, B, C, H, W, Cout, geom)     # [B*H*W, K*Cout]
-            W2T = weight.permute(1, 2, 3, 0).reshape(C, -1)          # [C, K*Cout]
-            if cl_in:     # the input was channels-last: so is its gradient ([B*H*W, C] from one GEMM, viewed as [B, C, H, W])
-                grad_input = torch.mm(S_T, W2T.t()).view(B, H, W, C).permute(0, 3, 1, 2)
-            else:
-                grad_input = torch.bmm(W2T.unsqueeze(0).expand(B, -1, -1), S_T.view(B, H * W, -1).transpose(1, 2)).view(B, C, H, W)
-    if need_weight:
-        if colT is None:
-            colT = _im2col_nhwc(xT, offset, mask, B, C, H, W, geom)  # [B*Ho*Wo, K*C]
-        grad_weight = torch.mm(g2.t(), colT).view(Cout, kH, kW, C).permute(0, 3, 1, 2)   # [Cout, C, kH, kW], channels-last strides
+            grad_input = torch.bmm(W2T.unsqueeze(0).expand(B, -1, -1), S_T.view(B, H * W, -1).transpose(1, 2)).view(B, C, H, W)
+    if grad_weight is not None:
+        grad_weight = grad_weight.view(-1, kH, kW, C).permute(0, 3, 1, 2)   # [Cout, C, kH, kW], channels-last strides
         if not cl_w:
             grad_weight = grad_weight.contiguous()
-    if need_bias:
-        grad_bias = g2.sum(0)
     return grad_input, grad_offset, grad_mask, grad_weight, grad_bias
 
 
@@ -1879,6 +1883,74 @@ def _grouped_weight_times_cols(weight, col, group, out):
         torch.mm(w2[g], col[g * Kg:(g + 1) * Kg], out=out[g * Mg:(g + 1) * Mg])
 
 
+def _sl(t, sl):
+    return None if t is None else t[sl]
+
+
+def _dcn_forward(input, weight, offset, mask, bias, output, geom, group, im2col_step, keep):
+    """what deform_conv_forward (mask and bias None) and modulated_deform_conv_forward share once their arguments are
+    checked and in `geom` order (kH, kW, padH, padW, dH, dW, dilH, dilW, dg): fused MFMA kernel -> channels-last
+    pipeline -> reference-layout kernels, `im2col_step` images at a time."""
+    B, _, H, W = input.shape
+    Cout = weight.size(0)
+    Ho, Wo = _out_hw(H, W, *geom[:8])
+    out = output.view(B, Cout, Ho, Wo)
+    if (not is_channels_last(input) and out.is_contiguous()
+            and _fused_dcn_forward(input, weight.contiguous(), offset, mask, None if bias is None else bias.to(input.dtype).contiguous(),
+                                   out, *geom[:8], group, geom[8])):
+        return
+    if (out.is_contiguous() or is_channels_last(out)) and _nhwc_ok(input, weight, group, geom[8]):
+        kept = _nhwc_forward(input, weight, offset, mask, bias, out, geom)
+        if keep is not None:
+            keep.append(kept)
+        return
+    input, weight = input.contiguous(), weight.contiguous()
+    for b0 in range(0, B, im2col_step):
+        sl = slice(b0, b0 + im2col_step)
+        col = deformable_im2col(input[sl], offset[sl], _sl(mask, sl), *geom)
+        buf = torch.empty((Cout, im2col_step * Ho * Wo), dtype=input.dtype, device=input.device)
+        _grouped_weight_times_cols(weight, col, group, buf)
+        out[sl].copy_(buf.view(Cout, im2col_step, Ho, Wo).transpose(0, 1))
+    if bias is not None:
+        out += bias.view(1, -1, 1, 1)
+
+
+def _ref_backward_input(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, geom, group, im2col_step):
+    """reference-layout kernels: columns = W^T * gradOut (deform_conv_cuda.cu:338-341 / :628-631), then col2im_coord
+    (overwrites grad_offset / grad_mask) and col2im (accumulates into grad_input), `im2col_step` images at a time"""
+    B, C = input.shape[:2]
+    Cout = weight.size(0)
+    n = im2col_step * grad_output.size(2) * grad_output.size(3)
+    Mg, Kg = Cout // group, (C // group) * geom[0] * geom[1]
+    w2 = weight.reshape(group, Mg, Kg)
+    for b0 in range(0, B, im2col_step):
+        sl = slice(b0, b0 + im2col_step)
+        go = grad_output[sl].transpose(0, 1).reshape(Cout, n)
+        col = torch.empty((group * Kg, n), dtype=input.dtype, device=input.device)
+        for g in range(group):
+            torch.mm(w2[g].t(), go[g * Mg:(g + 1) * Mg], out=col[g * Kg:(g + 1) * Kg])
+        deformable_col2im_coord(col, input[sl], offset[sl], _sl(mask, sl), grad_offset[sl], _sl(grad_mask, sl), *geom)
+        deformable_col2im(col, offset[sl], _sl(mask, sl), grad_input[sl], *geom)
+
+
+def _ref_backward_parameters(input, offset, mask, grad_output, grad_weight, grad_bias, geom, group, scale, im2col_step):
+    """reference-layout kernels: grad_weight += scale * gradOut * cols^T (deform_conv_cuda.cu:466-472 / :666-670) and
+    grad_bias += gradOut * ones (:671-676), `im2col_step` images at a time"""
+    B, C = input.shape[:2]
+    Cout = grad_weight.size(0)
+    n = im2col_step * grad_output.size(2) * grad_output.size(3)
+    Mg, Kg = Cout // group, (C // group) * geom[0] * geom[1]
+    gw = grad_weight.view(group, Mg, Kg)
+    for b0 in range(0, B, im2col_step):
+        sl = slice(b0, b0 + im2col_step)
+        col = deformable_im2col(input[sl], offset[sl], _sl(mask, sl), *geom)
+        go = grad_output[sl].transpose(0, 1).reshape(Cout, n)
+        for g in range(group):
+            gw[g].addmm_(go[g * Mg:(g + 1) * Mg], col[g * Kg:(g + 1) * Kg].t(), beta=1.0, alpha=float(scale))
+        if grad_bias is not None:
+            grad_bias += go.sum(1)
+
+
 def deform_conv_forward(input, weight, offset, output, columns, ones, kW, kH, dW, dH, padW, padH,
                         dilationW, dilationH, group, deformable_group, im2col_step, keep=None):
     """reference csrc/deform_conv.h:11-42 / csrc/cuda/deform_conv_cuda.cu:158-266.
@@ -1889,31 +1961,11 @@ def deform_conv_forward(input, weight, offset, output, columns, ones, kW, kH, dW
     # (a channels-last weight — a model switched to channels-last carries its 4-d parameters that way — IS the tap-major matrix
     #  the channels-last pipeline multiplies with: _w_tap_major is a view of it, no copy launch)
     input, offset, weight = _dcn_in(input), offset.contiguous(), _dcn_in(weight)
-    Ho, Wo = _shape_check(input, offset, None, weight, kH, kW, dH, dW, padH, padW, dilationH,
-                          dilationW, group, deformable_group)
-    B, C = input.shape[:2]
-    Cout = weight.size(0)
-    if B % im2col_step != 0:
+    _shape_check(input, offset, None, weight, kH, kW, dH, dW, padH, padW, dilationH, dilationW, group, deformable_group)
+    if input.size(0) % im2col_step != 0:
         raise RuntimeError("im2col step must divide batchsize")
-    out = output.view(B, Cout, Ho, Wo)
-    cl = is_channels_last(input)
-    if not cl and out.is_contiguous() and _fused_dcn_forward(input, weight.contiguous(), offset, None, None, out, kH, kW, padH, padW, dH, dW,
-                                                             dilationH, dilationW, group, deformable_group):
-        return 1
-    if (out.is_contiguous() or is_channels_last(out)) and _nhwc_ok(input, weight, group, deformable_group):
-        kept = _nhwc_forward(input, weight, offset, None, None, out, (kH, kW, padH, padW, dH, dW, dilationH, dilationW, deformable_group))
-        if keep is not None:
-            keep.append(kept)
-        return 1
-    weight = weight.contiguous()
-    input = input.contiguous()
-    for b0 in range(0, B, im2col_step):
-        sl = slice(b0, b0 + im2col_step)
-        col = deformable_im2col(input[sl], offset[sl], None, kH, kW, padH, padW, dH, dW, dilationH,
-                                dilationW, deformable_group)
-        buf = torch.empty((Cout, im2col_step * Ho * Wo), dtype=input.dtype, device=input.device)
-        _grouped_weight_times_cols(weight, col, group, buf)
-        out[sl].copy_(buf.view(Cout, im2col_step, Ho, Wo).transpose(0, 1))
+    _dcn_forward(input, weight, offset, None, None, output, (kH, kW, padH, padW, dH, dW, dilationH, dilationW, deformable_group),
+                 group, im2col_step, keep)
     return 1
 
 
@@ -1925,27 +1977,12 @@ def deform_conv_backward_input(input, offset, gradOutput, gradInput, gradOffset,
     _dcn_check("deform_conv_backward_input", input, offset, gradOutput, gradInput, gradOffset, weight)
     input, offset = input.contiguous(), offset.contiguous()
     gradOutput, weight = gradOutput.contiguous(), weight.contiguous()
-    Ho, Wo = _shape_check(input, offset, gradOutput, weight, kH, kW, dH, dW, padH, padW, dilationH,
-                          dilationW, group, deformable_group)
-    B, C = input.shape[:2]
-    Cout = weight.size(0)
-    if gradInput.is_contiguous() and gradOffset.is_contiguous() and _nhwc_ok(
-            input, weight, group, deformable_group, (kH, kW, padH, padW, dH, dW, dilationH, dilationW, deformable_group)):
-        _nhwc_backward(input, weight, offset, None, gradOutput, gradInput, gradOffset, None, None, None,
-                       (kH, kW, padH, padW, dH, dW, dilationH, dilationW, deformable_group))
-        return 1
-    Mg, Kg = Cout // group, (C // group) * kH * kW
-    w2 = weight.reshape(group, Mg, Kg)
-    for b0 in range(0, B, im2col_step):
-        sl = slice(b0, b0 + im2col_step)
-        go = gradOutput[sl].transpose(0, 1).reshape(Cout, im2col_step * Ho * Wo)
-        col = torch.empty((C * kH * kW, im2col_step * Ho * Wo), dtype=input.dtype, device=input.device)
-        for g in range(group):  # columns = W^T * gradOut  (:338-341)
-            torch.mm(w2[g].t(), go[g * Mg:(g + 1) * Mg], out=col[g * Kg:(g + 1) * Kg])
-        deformable_col2im_coord(col, input[sl], offset[sl], None, gradOffset[sl], None, kH, kW, padH,
-                                padW, dH, dW, dilationH, dilationW, deformable_group)
-        deformable_col2im(col, offset[sl], None, gradInput[sl], kH, kW, padH, padW, dH, dW, dilationH,
-                          dilationW, deformable_group)
+    _shape_check(input, offset, gradOutput, weight, kH, kW, dH, dW, padH, padW, dilationH, dilationW, group, deformable_group)
+    geom = (kH, kW, padH, padW, dH, dW, dilationH, dilationW, deformable_group)
+    if gradInput.is_contiguous() and gradOffset.is_contiguous() and _nhwc_ok(input, weight, group, deformable_group, geom):
+        _nhwc_backward(input, weight, offset, None, gradOutput, gradInput, gradOffset, None, None, None, geom)
+    else:
+        _ref_backward_input(input, weight, offset, None, gradOutput, gradInput, gradOffset, None, geom, group, im2col_step)
     return 1
 
 
@@ -1956,25 +1993,27 @@ def deform_conv_backward_parameters(input, offset, gradOutput, gradWeight, colum
     gradWeight += scale * gradOut * cols^T.  Returns 1."""
     _dcn_check("deform_conv_backward_parameters", input, offset, gradOutput, gradWeight)
     input, offset, gradOutput = input.contiguous(), offset.contiguous(), gradOutput.contiguous()
-    Ho, Wo = _shape_check(input, offset, gradOutput, gradWeight, kH, kW, dH, dW, padH, padW,
-                          dilationH, dilationW, group, deformable_group)
-    B, C = input.shape[:2]
-    Cout = gradWeight.size(0)
+    _shape_check(input, offset, gradOutput, gradWeight, kH, kW, dH, dW, padH, padW, dilationH, dilationW, group, deformable_group)
+    geom = (kH, kW, padH, padW, dH, dW, dilationH, dilationW, deformable_group)
     if gradWeight.is_contiguous() and _nhwc_ok(input, gradWeight, group, deformable_group):
-        _nhwc_backward(input, None, offset, None, gradOutput, None, None, None, gradWeight, None,
-                       (kH, kW, padH, padW, dH, dW, dilationH, dilationW, deformable_group), scale=scale)
-        return 1
-    Mg, Kg = Cout // group, (C // group) * kH * kW
-    gw = gradWeight.view(group, Mg, Kg)
-    for b0 in range(0, B, im2col_step):
-        sl = slice(b0, b0 + im2col_step)
-        col = deformable_im2col(input[sl], offset[sl], None, kH, kW, padH, padW, dH, dW, dilationH,
-                                dilationW, deformable_group)
-        go = gradOutput[sl].transpose(0, 1).reshape(Cout, im2col_step * Ho * Wo)
-        for g in range(group):  # :466-472
-            gw[g].addmm_(go[g * Mg:(g + 1) * Mg], col[g * Kg:(g + 1) * Kg].t(), beta=1.0,
-                         alpha=float(scale))
+        _nhwc_backward(input, None, offset, None, gradOutput, None, None, None, gradWeight, None, geom, scale=scale)
+    else:
+        _ref_backward_parameters(input, offset, None, gradOutput, gradWeight, None, geom, group, scale, im2col_step)
     return 1
+
+
+def _modulated_check(input, weight, kernel_h, kernel_w, group, channels_last_too):
+    """the reference's v2 checks (same texts); `channels_last_too`: the forward also takes a channels-last input and
+    weight (a model switched to channels-last carries its 4-d parameters that way)"""
+    if not input.is_contiguous() and not (channels_last_too and is_channels_last(input)):
+        raise RuntimeError("input tensor has to be contiguous")
+    if not weight.is_contiguous() and not (channels_last_too and is_channels_last(weight)):
+        raise RuntimeError("weight tensor has to be contiguous")
+    if weight.size(2) != kernel_h or weight.size(3) != kernel_w:
+        raise RuntimeError("Input shape and kernel shape wont match: (%d x %d vs %d x %d)."
+                           % (kernel_h, kernel_w, weight.size(2), weight.size(3)))
+    if input.size(1) != weight.size(1) * group:
+        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (input.size(1), weight.size(1) * group))
 
 
 def modulated_deform_conv_forward(input, weight, bias, ones, offset, mask, output, columns, kernel_h,
@@ -1985,40 +2024,10 @@ def modulated_deform_conv_forward(input, weight, bias, ones, offset, mask, outpu
     The reference loops per image; one im2col + one GEMM per group over the whole batch gives the
     same sums."""
     _dcn_check("modulated_deform_conv_forward", input, weight, offset, mask, output)
-    cl = is_channels_last(input)
-    if not input.is_contiguous() and not cl:
-        raise RuntimeError("input tensor has to be contiguous")
-    if not weight.is_contiguous() and not is_channels_last(weight):
-        raise RuntimeError("weight tensor has to be contiguous")   # (or channels-last: a model switched to channels-last carries its 4-d parameters that way)
-    B, C, H, W = input.shape
-    Cout, Cker, kh_, kw_ = weight.shape
-    if kh_ != kernel_h or kw_ != kernel_w:
-        raise RuntimeError("Input shape and kernel shape wont match: (%d x %d vs %d x %d)."
-                           % (kernel_h, kernel_w, kh_, kw_))
-    if C != Cker * group:
-        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (C, Cker * group))
-    Ho, Wo = _out_hw(H, W, kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w, dilation_h, dilation_w)
-    offset, mask = offset.contiguous(), mask.contiguous()
-    out = output.view(B, Cout, Ho, Wo)
-    if not cl and out.is_contiguous() and _fused_dcn_forward(input, weight.contiguous(), offset, mask, bias.to(input.dtype).contiguous() if with_bias else None,
-                                                             out, kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w,
-                                                             dilation_h, dilation_w, group, deformable_group):
-        return
-    if (out.is_contiguous() or is_channels_last(out)) and _nhwc_ok(input, weight, group, deformable_group):
-        kept = _nhwc_forward(input, weight, offset, mask, bias if with_bias else None, out,
-                             (kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w, dilation_h, dilation_w, deformable_group))
-        if keep is not None:
-            keep.append(kept)
-        return
-    input, weight = input.contiguous(), weight.contiguous()
-    col = deformable_im2col(input, offset, mask, kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w,
-                            dilation_h, dilation_w, deformable_group)
-    buf = torch.empty((Cout, B * Ho * Wo), dtype=input.dtype, device=input.device)
-    _grouped_weight_times_cols(weight, col, group, buf)
-    out = output.view(B, Cout, Ho, Wo)
-    out.copy_(buf.view(Cout, B, Ho, Wo).transpose(0, 1))
-    if with_bias:
-        out += bias.view(1, -1, 1, 1)
+    _modulated_check(input, weight, kernel_h, kernel_w, group, True)
+    _dcn_forward(input, weight, offset.contiguous(), mask.contiguous(), bias if with_bias else None, output,
+                 (kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w, dilation_h, dilation_w, deformable_group),
+                 group, max(input.size(0), 1), keep)
 
 
 def modulated_deform_conv_backward(input, weight, bias, ones, offset, mask, columns, grad_input,
@@ -2030,40 +2039,17 @@ def modulated_deform_conv_backward(input, weight, bias, ones, offset, mask, colu
     overwritten."""
     _dcn_check("modulated_deform_conv_backward", input, weight, offset, mask, grad_input, grad_weight,
                grad_offset, grad_mask, grad_output)
-    if not input.is_contiguous():
-        raise RuntimeError("input tensor has to be contiguous")
-    if not weight.is_contiguous():
-        raise RuntimeError("weight tensor has to be contiguous")
-    B, C, H, W = input.shape
-    Cout, Cker, kh_, kw_ = weight.shape
-    if kh_ != kernel_h or kw_ != kernel_w:
-        raise RuntimeError("Input shape and kernel shape wont match: (%d x %d vs %d x %d)."
-                           % (kernel_h, kernel_w, kh_, kw_))
-    if C != Cker * group:
-        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (C, Cker * group))
-    Ho, Wo = _out_hw(H, W, kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w, dilation_h, dilation_w)
+    _modulated_check(input, weight, kernel_h, kernel_w, group, False)
     offset, mask, grad_output = offset.contiguous(), mask.contiguous(), grad_output.contiguous()
-    geom = (kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w, dilation_h, dilation_w,
-            deformable_group)
+    geom = (kernel_h, kernel_w, pad_h, pad_w, stride_h, stride_w, dilation_h, dilation_w, deformable_group)
+    grad_bias = grad_bias if with_bias else None
     if (grad_input.is_contiguous() and grad_weight.is_contiguous() and grad_offset.is_contiguous() and grad_mask.is_contiguous()
             and _nhwc_ok(input, weight, group, deformable_group, geom)):
-        _nhwc_backward(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight,
-                       grad_bias if with_bias else None, geom)
-        return
-    Mg, Kg = Cout // group, Cker * kernel_h * kernel_w
-    w2 = weight.reshape(group, Mg, Kg)
-    go = grad_output.transpose(0, 1).reshape(Cout, B * Ho * Wo)
-    col = torch.empty((C * kernel_h * kernel_w, B * Ho * Wo), dtype=input.dtype, device=input.device)
-    for g in range(group):  # columns = W^T * gradOut (:628-631)
-        torch.mm(w2[g].t(), go[g * Mg:(g + 1) * Mg], out=col[g * Kg:(g + 1) * Kg])
-    deformable_col2im_coord(col, input, offset, mask, grad_offset, grad_mask, *geom)
-    deformable_col2im(col, offset, mask, grad_input, *geom)
-    col = deformable_im2col(input, offset, mask, *geom)
-    gw = grad_weight.view(group, Mg, Kg)
-    for g in range(group):  # :666-670
-        gw[g].addmm_(go[g * Mg:(g + 1) * Mg], col[g * Kg:(g + 1) * Kg].t())
-    if with_bias:  # :671-676 gradOut * ones
-        grad_bias += go.sum(1)
+        _nhwc_backward(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias, geom)
+    else:
+        step = max(input.size(0), 1)
+        _ref_backward_input(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, geom, group, step)
+        _ref_backward_parameters(input, offset, mask, grad_output, grad_weight, grad_bias, geom, group, 1.0, step)
 
 
 def _psroi_args(name, input, bbox, trans, no_trans, part_size):

@@ -1185,6 +1185,23 @@ def test_deform_conv_backward_with_kept_forward_copies_equals_rebuild(modulated)
             torch.testing.assert_close(p_.float(), q_.float(), rtol=2e-3, atol=2e-3 * float(q_.float().abs().max()))
 
 
+@pytest.mark.parametrize("modulated", [False, True])
+def test_deform_conv_reference_named_backward_on_the_channels_last_plan(modulated):
+    """the reference-named backward entry points at B=2, C=Cout=64, 9x11 fp32 (the smallest shape the channels-last pipeline
+    serves): accumulate / overwrite semantics, `scale`, the oracle's gradients, the launches (tests/torch_refs.py)"""
+    import torch_refs
+    torch_refs.check_dcn_reference_names_in_plan(DEV, modulated, 1e-4)
+
+
+@pytest.mark.parametrize("modulated,channels_last", [(False, False), (True, False), (True, True)])
+def test_deform_conv_layer_launch_sequence_on_the_channels_last_plan(modulated, channels_last):
+    """layer forward + backward at the same shape, fp32 (half NCHW inputs may take the fused forward, which keeps nothing):
+    one im2col, the coordinate kernel and the col2im gather; two layout transposes for NCHW tensors, none for channels-last
+    ones, whose input gradient is channels-last; values against the oracle (tests/torch_refs.py)"""
+    import torch_refs
+    torch_refs.check_dcn_layer_in_plan(DEV, modulated, channels_last, 1e-4)
+
+
 # ============================================================================ fused FrozenBN
 @pytest.mark.parametrize("shape", [(2, 8, 25, 42), (1, 5, 7, 9), (2, 16, 40, 64), (3, 4, 1, 1)])
 @pytest.mark.parametrize("relu,res", [(False, False), (True, False), (True, True), (False, True)])

@@ -10,6 +10,7 @@ import torch
 import cpu_shim
 import oracle
 import synth
+from torch_refs import launches as _launches
 
 
 @pytest.fixture(autouse=True)
@@ -25,11 +26,16 @@ def _t(a):
 @pytest.mark.parametrize("modulated", [False, True])
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-4), (torch.float16, 3e-2)])
 @pytest.mark.parametrize("geo", [dict(C=16, Cout=24, H=13, W=17, k=3, pad=1, stride=1, dil=1, g=1, dg=1),
-                                 dict(C=32, Cout=32, H=12, W=10, k=3, pad=2, stride=2, dil=2, g=2, dg=2)])
+                                 dict(C=32, Cout=32, H=12, W=10, k=3, pad=2, stride=2, dil=2, g=2, dg=2),
+                                 dict(C=128, Cout=128, H=9, W=11, k=3, pad=1, stride=1, dil=1, g=1, dg=1)])
 def test_deform_conv_modules_forward_and_backward_equal_the_oracle(modulated, dtype, tol, geo):
     """DeformConv / ModulatedDeformConv (layers/dcn; reference layers/dcn/deform_conv_func.py:14-262): forward, and the
-    gradients w.r.t. input, offset, mask, weight and bias — through `_C.deform_conv_forward` / `deform_conv_backward_all`
-    (channels-last pipeline and the kept forward copies where the plan allows them, the im2col path elsewhere)"""
+    gradients w.r.t. input, offset, mask, weight and bias.  The channels-last plan needs channels / (16 bytes of elements)
+    to be a power of two in [16, 256] and groups == deformable_groups == 1: C = 16 and the grouped C = 32 geometry are
+    outside it in both dtypes and run the reference-layout kernels (`_C.deform_conv_forward` falls through to im2col + GEMM,
+    `deform_conv_backward_all` returns None, the reference-named backward entry points serve the call); C = 128 is inside it
+    in both (128/4 = 32, 128/8 = 16) and runs the channels-last pipeline with the kept forward copies and
+    `deform_conv_backward_all`.  The launch counter says which of the two ran."""
     from maskrcnn_benchmark.layers import DeformConv, ModulatedDeformConv
     rng = np.random.RandomState(7)
     C, Cout, H, W, k = geo["C"], geo["Cout"], geo["H"], geo["W"], geo["k"]
@@ -55,12 +61,17 @@ def test_deform_conv_modules_forward_and_backward_equal_the_oracle(modulated, dt
     b = m.bias.detach().float().numpy() if modulated else None
     tx, toff = _t(x).to(dtype).requires_grad_(), _t(off).to(dtype).requires_grad_()
     tmask = _t(mask).to(dtype).requires_grad_() if modulated else None
-    out = m(tx, toff, tmask) if modulated else m(tx, toff)
+    with _launches() as fwd_calls:
+        out = m(tx, toff, tmask) if modulated else m(tx, toff)
+    assert fwd_calls.get("dcn_im2col_nhwc", 0) == (1 if C == 128 else 0), fwd_calls
     assert out.dtype == dtype and tuple(out.shape) == (B, Cout, Ho, Wo)
     ref = oracle.deform_conv_forward(x, off, mask, w, b, (pad, pad), (stride, stride), (dil, dil), g, dg)
     scale = max(1.0, float(np.abs(ref).max()))
     assert np.abs(out.detach().float().numpy() - ref).max() <= tol * scale
-    out.backward(_t(gout).to(dtype))
+    with _launches() as bwd_calls:
+        out.backward(_t(gout).to(dtype))
+    # in the plan: the kept column matrix is reused (no second im2col) and the pipeline's two backward kernels ran
+    assert bwd_calls.get("dcn_im2col_nhwc", 0) == 0 and bwd_calls.get("dcn_coord_nhwc", 0) == (1 if C == 128 else 0), bwd_calls
     gin, goff, gmask, gw, gb = oracle.deform_conv_backward(x, off, mask, w, gout, modulated, (pad, pad), (stride, stride),
                                                            (dil, dil), g, dg)
     for name, got, want in (("input", tx.grad, gin), ("offset", toff.grad, goff), ("mask", None if tmask is None else tmask.grad, gmask),
@@ -111,11 +122,13 @@ def test_deform_conv_modules_on_channels_last_tensors_equal_the_nchw_run(modulat
     """DeformConv / ModulatedDeformConv on a channels-last input (and channels-last parameters, as `model.to(memory_format=
     torch.channels_last)` leaves them): the channels-last pipeline reads the input in place, writes a channels-last output
     with one GEMM and returns a channels-last input gradient — same values as the NCHW call (the GEMMs' summation order
-    differs: 1e-5 fp32, 2e-2 half)."""
+    differs: 1e-5 fp32, 2e-2 half).  C = Cout = 128 is inside the channels-last plan in both dtypes (128/4 = 32, 128/8 = 16),
+    so both compared runs are pipeline runs (asserted with the launch counter): the NCHW one transposes the input and the
+    output gradient, the channels-last one launches no layout kernel at all."""
     from maskrcnn_benchmark import _C
     from maskrcnn_benchmark.layers import DeformConv, ModulatedDeformConv
     torch.manual_seed(3)
-    B, C, H, W, Cout, k = 2, 32, 11, 13, 32, 3
+    B, C, H, W, Cout, k = 2, 128, 11, 13, 128, 3
     x = torch.randn(B, C, H, W).to(dtype)
     off = (torch.randn(B, 2 * k * k, H, W) * 1.5).to(dtype)
     msk = torch.rand(B, k * k, H, W).to(dtype)
@@ -130,8 +143,13 @@ def test_deform_conv_modules_on_channels_last_tensors_equal_the_nchw_run(modulat
         xi = x.clone(memory_format=fmt).requires_grad_()
         oi = off.clone(memory_format=fmt).requires_grad_()
         args = (xi, oi) + ((msk.clone(memory_format=fmt).requires_grad_(),) if modulated else ())
-        y = layer(*args)
-        y.backward(g.clone(memory_format=fmt))
+        with _launches() as calls:
+            y = layer(*args)
+            y.backward(g.clone(memory_format=fmt))
+        want = {"dcn_im2col_nhwc": 1, "dcn_coord_nhwc": 1, "dcn_col2im_nhwc": 1}
+        if fmt is not cl:
+            want["dcn_to_nhwc"] = 2
+        assert {k: v for k, v in calls.items() if k.startswith("dcn_")} == want, (fmt, calls)
         return y, xi.grad, oi.grad, [p.grad.clone() for p in layer.parameters()]
 
     y0, gx0, go0, gp0 = run(torch.contiguous_format)
@@ -143,6 +161,30 @@ def test_deform_conv_modules_on_channels_last_tensors_equal_the_nchw_run(modulat
     assert torch.allclose(go1.float(), go0.float(), rtol=tol, atol=tol * float(go0.float().abs().max()))
     for a, b in zip(gp1, gp0):
         assert torch.allclose(a.float(), b.float(), rtol=tol, atol=tol * float(b.float().abs().max()) + 1e-6)
+
+
+@pytest.mark.parametrize("modulated", [False, True])
+def test_deform_conv_reference_named_backward_on_the_channels_last_plan(modulated):
+    """tests/torch_refs.py check_dcn_reference_names_in_plan: deform_conv_backward_input + deform_conv_backward_parameters
+    (scale 0.5) / modulated_deform_conv_backward at B=2, C=Cout=64, 9x11 fp32 — thin adapters over the pass the layers run"""
+    import torch_refs
+    torch_refs.check_dcn_reference_names_in_plan("cpu", modulated, 2e-4)
+
+
+@pytest.mark.parametrize("modulated", [False, True])
+def test_deform_conv_transposed_input_gradient_switch_equals_the_oracle(modulated):
+    """`_C.DCN_INPUT_GRAD = "transposed"` (env DETOPS_DCN_INPUT_GRAD), the A/B form of the input gradient — transposed
+    sampling of the output gradient + a GEMM instead of the col2im gather — is read in one place and gives the oracle's
+    gradients for NCHW and for channels-last tensors, with dcn_transposed_sample in place of dcn_col2im_nhwc"""
+    import torch_refs
+    from maskrcnn_benchmark import _C
+    prev = _C.DCN_INPUT_GRAD
+    _C.DCN_INPUT_GRAD = "transposed"
+    try:
+        for channels_last in (False, True):
+            torch_refs.check_dcn_layer_in_plan("cpu", modulated, channels_last, 2e-4, input_grad_kernel="dcn_transposed_sample")
+    finally:
+        _C.DCN_INPUT_GRAD = prev
 
 
 def test_nms_wrappers_equal_the_oracle_bit_exactly():

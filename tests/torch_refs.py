@@ -270,3 +270,108 @@ def check_fused_relu_non_finite(device, dtype, channels_last):
         colsum, bound = terms.sum((0, 2, 3)), terms[:, 0].numel() * 2.0 ** -24 * terms.abs().sum((0, 2, 3))
         got = bd.grad.cpu().double()
         assert bool(((got - colsum).abs() <= bound).all()), ("bias_act grad_bias C=%d" % Cb, got, colsum)
+
+
+# ---------------------------------------------------------------------------------------------- deformable conv, channels-last plan
+import contextlib  # noqa: E402
+
+
+@contextlib.contextmanager
+def launches():
+    """-> dict, filled on exit: calls per `_C._timed` name (the part of its format before "[") made inside the block,
+    counted by a `_C.KernelTimer(count_only=True)` (no events: works on CPU tensors under the host emulation too)"""
+    from maskrcnn_benchmark import _C
+    counts = {}
+    timer = _C.KernelTimer(count_only=True)
+    prev, _C.KERNEL_TIMER = _C.KERNEL_TIMER, timer
+    try:
+        yield counts
+    finally:
+        _C.KERNEL_TIMER = prev
+        for name, n in timer.calls.items():
+            key = (name[0] if type(name) is tuple else name).split("[")[0]
+            counts[key] = counts.get(key, 0) + n
+
+
+# the smallest shape inside the channels-last plan in fp32 (64 channels = 16 vectors of 16 bytes), odd map sides
+DCN_IN_PLAN = dict(B=2, C=64, H=9, W=11, k=3)
+
+
+def _dcn_in_plan_case(modulated, seed):
+    import synth
+    g = DCN_IN_PLAN
+    x, off, mask, wgt = synth.dcn_inputs(g["B"], g["C"], g["H"], g["W"], g["C"], g["k"], 1, modulated, seed=seed)
+    go = np.random.RandomState(seed + 1).randn(*x.shape).astype(np.float32)      # 3x3, pad 1, stride 1: output = input size
+    return x, off, mask, wgt, go
+
+
+def _near(got, want, tol, what):
+    err = float(np.abs(got.detach().cpu().numpy() - want).max())      # NaN (a buffer not overwritten) fails the comparison
+    assert err <= tol * max(1.0, float(np.abs(want).max())), (what, err)
+
+
+def check_dcn_reference_names_in_plan(device, modulated, tol):
+    """The reference-named backward entry points of `_C` (v1: deform_conv_backward_input + deform_conv_backward_parameters with
+    scale 0.5; v2: modulated_deform_conv_backward) on a shape the channels-last pipeline serves, against the oracle, with
+    the reference's ownership rules: gradInput / gradWeight / grad_bias are accumulated into (pre-filled with ones: the
+    result is 1 + gradient), gradOffset / grad_mask are overwritten in full (pre-filled with NaN); and the launches."""
+    import oracle
+    from maskrcnn_benchmark import _C
+    g = DCN_IN_PLAN
+    B, C, k = g["B"], g["C"], g["k"]
+    x, off, mask, wgt, go = _dcn_in_plan_case(modulated, 41)
+    t = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+    tx, toff, tw, tgo = t(x), t(off), t(wgt), t(go)
+    e = torch.empty(0, device=device)
+    gi, gw, gb = torch.ones_like(tx), torch.ones_like(tw), torch.ones(C, device=device)
+    goff, gm = torch.full_like(toff, float("nan")), None
+    geo = (k, k, 1, 1, 1, 1, 1, 1, 1, 1)           # kernel, stride, pad, dilation (square: either argument order), group, dg
+    with launches() as calls:
+        if modulated:
+            tm = t(mask)
+            gm = torch.full_like(tm, float("nan"))
+            _C.modulated_deform_conv_backward(tx, tw, torch.zeros(C, device=device), e, toff, tm, e, gi, gw, gb, goff, gm, tgo,
+                                              *geo, True)
+        else:
+            assert _C.deform_conv_backward_input(tx, toff, tgo, gi, goff, tw, e, *geo, B) == 1
+            assert _C.deform_conv_backward_parameters(tx, toff, tgo, gw, e, e, *geo, 0.5, B) == 1
+    # v1 asks in two calls, each of which transposes the input and the output gradient again
+    assert calls == {"dcn_to_nhwc": 2 if modulated else 4, "dcn_coord_nhwc": 1, "dcn_col2im_nhwc": 1, "dcn_im2col_nhwc": 1}, calls
+    rin, roff, rmask, rw, rb = oracle.deform_conv_backward(x, off, mask, wgt, go, modulated, (1, 1), (1, 1), (1, 1), 1, 1)
+    _near(gi, 1.0 + rin, tol, "gradInput")
+    _near(goff, roff, tol, "gradOffset")
+    _near(gw, 1.0 + (1.0 if modulated else 0.5) * rw, tol, "gradWeight")
+    if modulated:
+        _near(gm, rmask, tol, "grad_mask")
+        _near(gb, 1.0 + rb, tol, "grad_bias")
+
+
+def check_dcn_layer_in_plan(device, modulated, channels_last, tol, input_grad_kernel="dcn_col2im_nhwc"):
+    """deform_conv / modulated_deform_conv (layers/dcn) forward + backward on a shape the channels-last pipeline serves,
+    NCHW or everything (input, offset, mask, weight, upstream gradient) channels-last: the oracle's output and gradients,
+    and the launch sequence — one im2col (the forward's column matrix is kept for the backward pass), the coordinate kernel,
+    `input_grad_kernel`, and the two layout transposes (input, output gradient) that only NCHW tensors need."""
+    import oracle
+    from maskrcnn_benchmark import _C
+    from maskrcnn_benchmark.layers import deform_conv, modulated_deform_conv
+    x, off, mask, wgt, go = _dcn_in_plan_case(modulated, 43)
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    t = lambda a: torch.from_numpy(a).to(device).contiguous(memory_format=fmt)  # noqa: E731
+    tx, toff, tw = (t(a).requires_grad_() for a in (x, off, wgt))
+    tm = t(mask).requires_grad_() if modulated else None
+    with launches() as calls:
+        y = modulated_deform_conv(tx, toff, tm, tw, None, 1, 1, 1, 1, 1) if modulated else deform_conv(tx, toff, tw, 1, 1, 1, 1, 1)
+        y.backward(t(go))
+    want = {"dcn_im2col_nhwc": 1, "dcn_coord_nhwc": 1, input_grad_kernel: 1}
+    if not channels_last:
+        want["dcn_to_nhwc"] = 2
+    assert {k: v for k, v in calls.items() if k.startswith("dcn_")} == want, calls
+    assert _C.is_channels_last(y) == channels_last and _C.is_channels_last(tx.grad) == channels_last
+    og = ((1, 1), (1, 1), (1, 1), 1, 1)
+    _near(y, oracle.deform_conv_forward(x, off, mask, wgt, None, *og), tol, "output")
+    rin, roff, rmask, rw, _ = oracle.deform_conv_backward(x, off, mask, wgt, go, False, *og)
+    _near(tx.grad, rin, tol, "input gradient")
+    _near(toff.grad, roff, tol, "offset gradient")
+    _near(tw.grad, rw, tol, "weight gradient")
+    if modulated:
+        _near(tm.grad, rmask, tol, "mask gradient")
