@@ -11,7 +11,7 @@
 // into `partials`; a second small launch adds the workgroups' partials in index order: deterministic, no atomics.
 #include <algorithm>
 
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -19,21 +19,6 @@ constexpr int kBaThreads = 256;
 constexpr int kBaV = 4;                               // floats per thread and vector
 constexpr int kBaSpan = kBaThreads * kBaV;            // elements a workgroup covers per pass: C must divide it
 constexpr int kBaMaxBlocks = 512;
-
-template <typename T> struct BaIo;
-template <> struct BaIo<float> {
-  static __device__ __forceinline__ float ld(float v) { return v; }
-  static __device__ __forceinline__ float st(float v) { return v; }
-};
-template <> struct BaIo<__half> {
-  static __device__ __forceinline__ float ld(__half v) { return __half2float(v); }
-  static __device__ __forceinline__ __half st(float v) { return __float2half(v); }
-};
-template <> struct BaIo<__hip_bfloat16> {
-  static __device__ __forceinline__ float ld(__hip_bfloat16 v) { return __bfloat162float(v); }
-  static __device__ __forceinline__ __hip_bfloat16 st(float v) { return __float2bfloat16(v); }
-};
-template <typename T> struct alignas(sizeof(T) * kBaV) BaVec { T v[kBaV]; };
 
 // g = relu ? (y <= 0 ? 0 : gy) : gy ;  grad_x = g ;  partial[block][c] = sum over the block's rows of g[., c]  (fp32 sums;
 // T = float | __half | __hip_bfloat16 storage: the autocast configurations)
@@ -45,7 +30,7 @@ bias_act_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, T* _
   const int tid = threadIdx.x;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBaThreads;      // in vectors; stride * 4 is a multiple of C
   float acc[kBaV] = {0.f, 0.f, 0.f, 0.f};
-  using VT = BaVec<T>;
+  using VT = Vec<T, kBaV>;
   const VT* gv = reinterpret_cast<const VT*>(gy);
   const VT* yv = reinterpret_cast<const VT*>(y);
   VT* xo = reinterpret_cast<VT*>(gx);
@@ -55,13 +40,13 @@ bias_act_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, T* _
       const VT m = yv[i];
 #pragma unroll
       for (int j = 0; j < kBaV; ++j)
-        if (BaIo<T>::ld(m.v[j]) <= 0.f) g.v[j] = BaIo<T>::st(0.f);   // threshold_backward: passes where y is NaN
+        if (Io<T>::ld(m.v[j]) <= 0.f) g.v[j] = Io<T>::st(0.f);   // threshold_backward: passes where y is NaN
       xo[i] = g;
     } else if (gx != gy) {
       xo[i] = g;
     }
 #pragma unroll
-    for (int j = 0; j < kBaV; ++j) acc[j] += BaIo<T>::ld(g.v[j]);
+    for (int j = 0; j < kBaV; ++j) acc[j] += Io<T>::ld(g.v[j]);
   }
   // threads t, t + C/4, t + 2C/4, ... hold sums of the same channels: add them in thread order
 #pragma unroll
@@ -109,7 +94,7 @@ column_sum_kernel(const T* __restrict__ x, float* __restrict__ partials, int C, 
   float s = 0.f;
   if (c < C)
     for (int64_t r = static_cast<int64_t>(blockIdx.x) * rpb + rl; r < rows; r += static_cast<int64_t>(gridDim.x) * rpb)
-      s += BaIo<T>::ld(x[r * C + c]);
+      s += Io<T>::ld(x[r * C + c]);
   red[tid] = s;
   __syncthreads();
   if (rl == 0 && c < C) {
@@ -149,11 +134,11 @@ int bias_act_backward(const void* grad_y, const void* y, void* grad_x, float* gr
   const T* gp = static_cast<const T*>(grad_y);
   const T* yp = static_cast<const T*>(y);
   T* xp = static_cast<T*>(grad_x);
-  if (relu)
-    hipLaunchKernelGGL((bias_act_bwd_nhwc_kernel<T, true>), dim3(blocks), dim3(kBaThreads), 0, st, gp, yp, xp, partials, C, nvec);
-  else
-    hipLaunchKernelGGL((bias_act_bwd_nhwc_kernel<T, false>), dim3(blocks), dim3(kBaThreads), 0, st, gp, yp, xp, partials, C, nvec);
-  int e = launch_status();
+  int e = dispatch_bool(relu, [&](auto r) {
+    hipLaunchKernelGGL((bias_act_bwd_nhwc_kernel<T, decltype(r)::value>), dim3(blocks), dim3(kBaThreads), 0, st, gp, yp, xp, partials, C,
+                       nvec);
+    return launch_status();
+  });
   if (e) return e;
   hipLaunchKernelGGL(bias_grad_finish_kernel, dim3(static_cast<unsigned>(ceil_div64(C, kBfCh))), dim3(kBfCh * kBfRows), 0, st, partials,
                      grad_bias, C, blocks);
@@ -171,12 +156,9 @@ DETOPS_API int detops_bias_act_backward_nhwc(const void* grad_y, const void* y, 
   if (!grad_y || !grad_x || !grad_bias || (relu && !y) || !workspace) return DETOPS_EINVAL;
   hipStream_t st = as_stream(stream);
   if (rows == 0) { DETOPS_HIP_TRY(hipMemsetAsync(grad_bias, 0, sizeof(float) * C, st)); return 0; }
-  switch (dtype) {
-    case DETOPS_F32: return bias_act_backward<float>(grad_y, y, grad_x, grad_bias, rows, C, relu, workspace, workspace_bytes, st);
-    case DETOPS_F16: return bias_act_backward<__half>(grad_y, y, grad_x, grad_bias, rows, C, relu, workspace, workspace_bytes, st);
-    case DETOPS_BF16: return bias_act_backward<__hip_bfloat16>(grad_y, y, grad_x, grad_bias, rows, C, relu, workspace, workspace_bytes, st);
-    default: return DETOPS_EUNSUPPORTED;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return bias_act_backward<typename decltype(tag)::type>(grad_y, y, grad_x, grad_bias, rows, C, relu, workspace, workspace_bytes, st);
+  });
 }
 
 DETOPS_API int detops_bias_act_backward_nhwc_f32(const float* grad_y, const float* y, float* grad_x, float* grad_bias,
@@ -220,12 +202,9 @@ DETOPS_API int detops_column_sum(const void* x, float* out, int dtype, int64_t r
   if (!out || (rows > 0 && (!x || !workspace))) return DETOPS_EINVAL;
   hipStream_t st = as_stream(stream);
   if (rows == 0) { DETOPS_HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * C, st)); return 0; }
-  switch (dtype) {
-    case DETOPS_F32: return column_sum_run<float>(x, out, rows, C, workspace, workspace_bytes, st);
-    case DETOPS_F16: return column_sum_run<__half>(x, out, rows, C, workspace, workspace_bytes, st);
-    case DETOPS_BF16: return column_sum_run<__hip_bfloat16>(x, out, rows, C, workspace, workspace_bytes, st);
-    default: return DETOPS_EUNSUPPORTED;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return column_sum_run<typename decltype(tag)::type>(x, out, rows, C, workspace, workspace_bytes, st);
+  });
 }
 
 DETOPS_API int detops_column_sum_f32(const float* x, float* out, int64_t rows, int C, void* workspace, size_t workspace_bytes,

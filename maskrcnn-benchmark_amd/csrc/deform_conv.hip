@@ -13,17 +13,14 @@
 #include <cstdlib>
 
 #include "detops_devlib.h"
+#include "detops_dtype.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 
-template <typename T> __device__ __forceinline__ float ld(const T* p) { return static_cast<float>(*p); }
-template <> __device__ __forceinline__ float ld<__half>(const __half* p) { return __half2float(*p); }
-template <> __device__ __forceinline__ float ld<__hip_bfloat16>(const __hip_bfloat16* p) { return __bfloat162float(*p); }
-template <typename T> __device__ __forceinline__ void st(T* p, float v) { *p = static_cast<T>(v); }
-template <> __device__ __forceinline__ void st<__half>(__half* p, float v) { *p = __float2half(v); }
-template <> __device__ __forceinline__ void st<__hip_bfloat16>(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }
+template <typename T> __device__ __forceinline__ float ld(const T* p) { return Io<T>::ld(*p); }
+template <typename T> __device__ __forceinline__ void st(T* p, float v) { *p = Io<T>::st(v); }
 
 __device__ __forceinline__ void atomic_add_t(float* p, float v) { atomicAdd(p, v); }
 __device__ __forceinline__ void atomic_add_t(__half* p, float v) {
@@ -1818,14 +1815,6 @@ int col2im_nhwc_t(const void* colsG, const void* offset, const void* mask, void*
 
 }  // namespace
 
-#define DETOPS_DTYPE_SWITCH(dtype, CALL)                              \
-  switch (dtype) {                                                    \
-    case DETOPS_F32: return CALL(float);                              \
-    case DETOPS_F16: return CALL(__half);                             \
-    case DETOPS_BF16: return CALL(__hip_bfloat16);                    \
-    default: return DETOPS_EUNSUPPORTED;                              \
-  }
-
 DETOPS_API int detops_deformable_im2col(const void* im, const void* offset, const void* mask,
                                         void* col, int dtype, int B, int C, int H, int W, int kh,
                                         int kw, int pad_h, int pad_w, int stride_h, int stride_w,
@@ -1837,9 +1826,9 @@ DETOPS_API int detops_deformable_im2col(const void* im, const void* offset, cons
     return rc;
   if (B == 0) return 0;
   if (!im || !offset || !col) return DETOPS_EINVAL;
-#define CALL(T) im2col_t<T>(im, offset, mask, col, g, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return im2col_t<typename decltype(tag)::type>(im, offset, mask, col, g, as_stream(stream));
+  });
 }
 
 DETOPS_API int detops_deformable_col2im(const void* col, const void* offset, const void* mask,
@@ -1853,9 +1842,9 @@ DETOPS_API int detops_deformable_col2im(const void* col, const void* offset, con
     return rc;
   if (B == 0) return 0;
   if (!col || !offset || !grad_im) return DETOPS_EINVAL;
-#define CALL(T) col2im_t<T>(col, offset, mask, grad_im, g, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return col2im_t<typename decltype(tag)::type>(col, offset, mask, grad_im, g, as_stream(stream));
+  });
 }
 
 DETOPS_API size_t detops_deformable_col2im_workspace_bytes(int B, int C, int H, int W, int kh, int kw,
@@ -1895,20 +1884,20 @@ DETOPS_API int detops_deformable_col2im_ws(const void* col, const void* offset, 
   if (want_ell && workspace) {
     EllPlan E;
     if (ell_plan(g, E) && workspace_bytes >= E.total) {
-#define CALL(T) col2im_ell_t<T>(col, offset, mask, grad_im, g, E, workspace, as_stream(stream))
-      DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+      return dispatch_dtype(dtype, [&](auto tag) {
+        return col2im_ell_t<typename decltype(tag)::type>(col, offset, mask, grad_im, g, E, workspace, as_stream(stream));
+      });
     }
   }
   const bool scatter = !want_gather || !workspace || !gather_plan(g, P) || workspace_bytes < P.total;
   if (scatter) {
-#define CALL(T) col2im_t<T>(col, offset, mask, grad_im, g, as_stream(stream))
-    DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+    return dispatch_dtype(dtype, [&](auto tag) {
+      return col2im_t<typename decltype(tag)::type>(col, offset, mask, grad_im, g, as_stream(stream));
+    });
   }
-#define CALL(T) col2im_gather_t<T>(col, offset, mask, grad_im, g, P, workspace, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return col2im_gather_t<typename decltype(tag)::type>(col, offset, mask, grad_im, g, P, workspace, as_stream(stream));
+  });
 }
 
 DETOPS_API int detops_deformable_col2im_coord(const void* col, const void* im, const void* offset,
@@ -1923,9 +1912,9 @@ DETOPS_API int detops_deformable_col2im_coord(const void* col, const void* im, c
     return rc;
   if (B == 0) return 0;
   if (!col || !im || !offset || !grad_offset || (mask && !grad_mask)) return DETOPS_EINVAL;
-#define CALL(T) coord_t<T>(col, im, offset, mask, grad_offset, grad_mask, g, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return coord_t<typename decltype(tag)::type>(col, im, offset, mask, grad_offset, grad_mask, g, as_stream(stream));
+  });
 }
 
 
@@ -1965,9 +1954,9 @@ DETOPS_API int detops_nchw_to_nhwc(const void* in, void* out, int dtype, int B, 
   if (B < 0 || C < 0 || HW < 0) return DETOPS_EINVAL;
   if (B == 0 || C == 0 || HW == 0) return 0;
   if (!in || !out) return DETOPS_EINVAL;
-#define CALL(T) nchw_to_nhwc_t<T>(in, out, B, C, HW, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return nchw_to_nhwc_t<typename decltype(tag)::type>(in, out, B, C, HW, as_stream(stream));
+  });
 }
 
 // 1 when the channels-last kernels serve this shape (deformable_group == 1, channels / (16 bytes of elements) a power of
@@ -1987,9 +1976,9 @@ DETOPS_API int detops_deformable_im2col_nhwc(const void* xT, const void* offset,
   if (int rc = make_geom(g, B, C, H, W, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, deformable_group)) return rc;
   if (B == 0) return 0;
   if (!xT || !offset || !colT) return DETOPS_EINVAL;
-#define CALL(T) im2col_nhwc_t<T>(xT, offset, mask, colT, g, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return im2col_nhwc_t<typename decltype(tag)::type>(xT, offset, mask, colT, g, as_stream(stream));
+  });
 }
 
 DETOPS_API int detops_deformable_coord_nhwc(const void* colsG_T, const void* xT, const void* offset, const void* mask,
@@ -2000,9 +1989,9 @@ DETOPS_API int detops_deformable_coord_nhwc(const void* colsG_T, const void* xT,
   if (int rc = make_geom(g, B, C, H, W, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, deformable_group)) return rc;
   if (B == 0) return 0;
   if (!colsG_T || !xT || !offset || !grad_offset) return DETOPS_EINVAL;
-#define CALL(T) coord_nhwc_t<T>(colsG_T, xT, offset, mask, grad_offset, grad_mask, g, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return coord_nhwc_t<typename decltype(tag)::type>(colsG_T, xT, offset, mask, grad_offset, grad_mask, g, as_stream(stream));
+  });
 }
 
 DETOPS_API size_t detops_deformable_transposed_sample_workspace_bytes(int B, int C, int H, int W, int kh, int kw, int pad_h, int pad_w,
@@ -2026,9 +2015,9 @@ DETOPS_API int detops_deformable_transposed_sample(const void* gT, const void* o
   EllPlan P;
   if (g.dg != 1 || !ell_plan(g, P)) return DETOPS_EUNSUPPORTED;
   if (!workspace || workspace_bytes < P.total) return DETOPS_EWORKSPACE;
-#define CALL(T) sampleT_t<T>(gT, offset, mask, S_T, g, Cout, P, workspace, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return sampleT_t<typename decltype(tag)::type>(gT, offset, mask, S_T, g, Cout, P, workspace, as_stream(stream));
+  });
 }
 
 // grad_in_T [B, H*W, C] (the channels-last input gradient) from the channel-fastest column gradient colsG_T [B*Ho*Wo, kh*kw, C]:
@@ -2044,7 +2033,7 @@ DETOPS_API int detops_deformable_col2im_nhwc(const void* colsG_T, const void* of
   EllPlan P;
   if (g.dg != 1 || !ell_plan(g, P)) return DETOPS_EUNSUPPORTED;
   if (!workspace || workspace_bytes < P.total) return DETOPS_EWORKSPACE;
-#define CALL(T) col2im_nhwc_t<T>(colsG_T, offset, mask, grad_in_T, g, P, workspace, as_stream(stream))
-  DETOPS_DTYPE_SWITCH(dtype, CALL)
-#undef CALL
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return col2im_nhwc_t<typename decltype(tag)::type>(colsG_T, offset, mask, grad_in_T, g, P, workspace, as_stream(stream));
+  });
 }

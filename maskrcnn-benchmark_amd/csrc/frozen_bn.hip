@@ -8,27 +8,11 @@
 // backward's ReLU-mask + scale becomes one pass as well.  Pure HBM streaming: one workgroup row
 // per (n, c) plane so scale/bias are wave-uniform scalars, 16-byte vector accesses when the plane
 // size allows it.
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-template <typename T> struct Cvt;
-template <> struct Cvt<float> {
-  static __device__ __forceinline__ float load(const float v) { return v; }
-  static __device__ __forceinline__ float store(float v) { return v; }
-};
-template <> struct Cvt<__half> {
-  static __device__ __forceinline__ float load(const __half v) { return __half2float(v); }
-  static __device__ __forceinline__ __half store(float v) { return __float2half(v); }
-};
-template <> struct Cvt<__hip_bfloat16> {
-  static __device__ __forceinline__ float load(const __hip_bfloat16 v) { return __bfloat162float(v); }
-  static __device__ __forceinline__ __hip_bfloat16 store(float v) { return __float2bfloat16(v); }
-};
-
-template <typename T, int V> struct alignas(sizeof(T) * V) Vec { T v[V]; };
 
 // y = [relu]( x * scale[c] + bias[c] [+ residual] )
 template <typename T, int V, bool kRelu, bool kRes>
@@ -52,10 +36,10 @@ frozen_bn_fwd_kernel(const T* __restrict__ x, const float* __restrict__ scale, c
     VT o;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float t = Cvt<T>::load(a.v[j]) * s + b;       // torch: (x * scale) + bias, two roundings in fp32
-      if (kRes) t = t + Cvt<T>::load(r.v[j]);
+      float t = Io<T>::ld(a.v[j]) * s + b;       // torch: (x * scale) + bias, two roundings in fp32
+      if (kRes) t = t + Io<T>::ld(r.v[j]);
       if (kRelu) t = t <= 0.f ? 0.f : t;         // torch.relu: NaN stays NaN
-      o.v[j] = Cvt<T>::store(t);
+      o.v[j] = Io<T>::st(t);
     }
     yv[i] = o;
   }
@@ -82,12 +66,12 @@ frozen_bn_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ y, const fl
     VT ox, orr;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float t = Cvt<T>::load(g.v[j]);
-      if (kRelu && Cvt<T>::load(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
+      float t = Io<T>::ld(g.v[j]);
+      if (kRelu && Io<T>::ld(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
       float p = t * s;
       DETOPS_F32_VALUE(p);                            // fp32 product, then the cast: torch's `(g * s).to(T)`
-      ox.v[j] = Cvt<T>::store(p);
-      if (kRes) orr.v[j] = Cvt<T>::store(t);
+      ox.v[j] = Io<T>::st(p);
+      if (kRes) orr.v[j] = Io<T>::st(t);
     }
     xo[i] = ox;
     if (kRes) ro[i] = orr;
@@ -126,10 +110,10 @@ frozen_bn_fwd_nhwc_kernel(const T* __restrict__ x, const float* __restrict__ sca
     VT o;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float t = Cvt<T>::load(a.v[j]) * s[j] + b[j];
-      if (kRes) t = t + Cvt<T>::load(r.v[j]);
+      float t = Io<T>::ld(a.v[j]) * s[j] + b[j];
+      if (kRes) t = t + Io<T>::ld(r.v[j]);
       if (kRelu) t = t <= 0.f ? 0.f : t;         // torch.relu: NaN stays NaN
-      o.v[j] = Cvt<T>::store(t);
+      o.v[j] = Io<T>::st(t);
     }
     yv[i] = o;
   }
@@ -163,12 +147,12 @@ frozen_bn_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, con
     VT ox, orr;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float t = Cvt<T>::load(g.v[j]);
-      if (kRelu && Cvt<T>::load(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
+      float t = Io<T>::ld(g.v[j]);
+      if (kRelu && Io<T>::ld(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
       float p = t * s[j];
       DETOPS_F32_VALUE(p);
-      ox.v[j] = Cvt<T>::store(p);
-      if (kRes) orr.v[j] = Cvt<T>::store(t);
+      ox.v[j] = Io<T>::st(p);
+      if (kRes) orr.v[j] = Io<T>::st(t);
     }
     xo[i] = ox;
     if (kRes) ro[i] = orr;
@@ -187,126 +171,84 @@ static inline unsigned nhwc_grid(int64_t nvec, int C, int V) {
   return static_cast<unsigned>(blocks);
 }
 
-template <typename T, int V>
-int launch_fwd_nhwc(const void* x, const float* scale, const float* bias, const void* res, void* y, int64_t n, int C,
-                    int relu, hipStream_t st) {
-  const int64_t nvec = n / V;
-  const dim3 grid(nhwc_grid(nvec, C, V));
-  const T* xp = static_cast<const T*>(x);
-  const T* rp = static_cast<const T*>(res);
-  T* yp = static_cast<T*>(y);
-#define FB_LAUNCH(R, S) hipLaunchKernelGGL((frozen_bn_fwd_nhwc_kernel<T, V, R, S>), grid, dim3(kThreads), 0, st, xp, scale, bias, rp, yp, C, nvec)
-  if (relu) { if (res) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
-  else      { if (res) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
-#undef FB_LAUNCH
-  return launch_status();
+// grid of the plane kernels: a row of workgroups per (n, c) plane, >= 4 vectors in flight per thread
+static inline dim3 plane_grid(int N, int C, int nvec) {
+  const int64_t chunks = ceil_div64(nvec, kThreads * 4);
+  return dim3(static_cast<unsigned>(N) * C, static_cast<unsigned>(chunks < 64 ? chunks : 64));
 }
 
-template <typename T, int V>
-int launch_bwd_nhwc(const void* gy, const void* y, const float* scale, void* gx, void* gres, int64_t n, int C, int relu,
-                    hipStream_t st) {
-  const int64_t nvec = n / V;
-  const dim3 grid(nhwc_grid(nvec, C, V));
-  const T* gp = static_cast<const T*>(gy);
-  const T* yp = static_cast<const T*>(y);
-  T* xp = static_cast<T*>(gx);
-  T* rp = static_cast<T*>(gres);
-#define FB_LAUNCH(R, S) hipLaunchKernelGGL((frozen_bn_bwd_nhwc_kernel<T, V, R, S>), grid, dim3(kThreads), 0, st, gp, yp, scale, xp, rp, C, nvec)
-  if (relu) { if (gres) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
-  else      { if (gres) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
-#undef FB_LAUNCH
-  return launch_status();
-}
-
-template <typename T, int V>
-int launch_fwd(const void* x, const float* scale, const float* bias, const void* res, void* y, int N, int C,
-               int HW, int relu, hipStream_t st) {
-  const int nvec = HW / V;
-  const int64_t chunks = ceil_div64(nvec, kThreads * 4);  // >= 4 vectors in flight per thread
-  const dim3 grid(static_cast<unsigned>(N) * C, static_cast<unsigned>(chunks < 64 ? chunks : 64));
-  const T* xp = static_cast<const T*>(x);
-  const T* rp = static_cast<const T*>(res);
-  T* yp = static_cast<T*>(y);
-#define FB_LAUNCH(R, S) hipLaunchKernelGGL((frozen_bn_fwd_kernel<T, V, R, S>), grid, dim3(kThreads), 0, st, xp, scale, bias, rp, yp, C, HW)
-  if (relu) { if (res) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
-  else      { if (res) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
-#undef FB_LAUNCH
-  return launch_status();
-}
-
-template <typename T, int V>
-int launch_bwd(const void* gy, const void* y, const float* scale, void* gx, void* gres, int N, int C, int HW,
+// NCHW: V | HW, so that every plane start stays aligned
+template <typename T>
+int launch_fwd(const void* x, const float* scale, const float* bias, const void* res, void* y, int N, int C, int HW,
                int relu, hipStream_t st) {
-  const int nvec = HW / V;
-  const int64_t chunks = ceil_div64(nvec, kThreads * 4);  // >= 4 vectors in flight per thread
-  const dim3 grid(static_cast<unsigned>(N) * C, static_cast<unsigned>(chunks < 64 ? chunks : 64));
+  const T* xp = static_cast<const T*>(x);
+  const T* rp = static_cast<const T*>(res);
+  T* yp = static_cast<T*>(y);
+  return dispatch_vec<T>(pick_vec<T>(HW, {x, res, y}), [&](auto vc) {
+    constexpr int V = decltype(vc)::value;
+    const dim3 grid = plane_grid(N, C, HW / V);
+    return dispatch_bools(relu, res != nullptr, [&](auto r, auto s) {
+      hipLaunchKernelGGL((frozen_bn_fwd_kernel<T, V, decltype(r)::value, decltype(s)::value>), grid, dim3(kThreads), 0, st,
+                         xp, scale, bias, rp, yp, C, HW);
+      return launch_status();
+    });
+  });
+}
+
+template <typename T>
+int launch_bwd(const void* gy, const void* y, const float* scale, void* gx, void* gres, int N, int C, int HW, int relu,
+               hipStream_t st) {
   const T* gp = static_cast<const T*>(gy);
   const T* yp = static_cast<const T*>(y);
   T* xp = static_cast<T*>(gx);
   T* rp = static_cast<T*>(gres);
-#define FB_LAUNCH(R, S) hipLaunchKernelGGL((frozen_bn_bwd_kernel<T, V, R, S>), grid, dim3(kThreads), 0, st, gp, yp, scale, xp, rp, C, HW)
-  if (relu) { if (gres) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
-  else      { if (gres) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
-#undef FB_LAUNCH
-  return launch_status();
-}
-
-// widest vector (in elements) such that every plane start stays aligned: V | HW and V*sizeof(T) <= 16
-template <typename T> int pick_vec(int HW, const void* a, const void* b, const void* c, const void* d) {
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
-                         reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d);
-  for (int v = 16 / static_cast<int>(sizeof(T)); v > 1; v >>= 1)
-    if (HW % v == 0 && (bits % (v * sizeof(T))) == 0) return v;
-  return 1;
-}
-
-template <typename T>
-int dispatch_fwd(const void* x, const float* scale, const float* bias, const void* res, void* y, int N, int C,
-                 int HW, int relu, hipStream_t st) {
-  switch (pick_vec<T>(HW, x, res, y, nullptr)) {
-    case 8: return launch_fwd<T, 8>(x, scale, bias, res, y, N, C, HW, relu, st);
-    case 4: return launch_fwd<T, 4>(x, scale, bias, res, y, N, C, HW, relu, st);
-    case 2: return launch_fwd<T, 2>(x, scale, bias, res, y, N, C, HW, relu, st);
-    default: return launch_fwd<T, 1>(x, scale, bias, res, y, N, C, HW, relu, st);
-  }
-}
-
-template <typename T>
-int dispatch_bwd(const void* gy, const void* y, const float* scale, void* gx, void* gres, int N, int C, int HW,
-                 int relu, hipStream_t st) {
-  switch (pick_vec<T>(HW, gy, y, gx, gres)) {
-    case 8: return launch_bwd<T, 8>(gy, y, scale, gx, gres, N, C, HW, relu, st);
-    case 4: return launch_bwd<T, 4>(gy, y, scale, gx, gres, N, C, HW, relu, st);
-    case 2: return launch_bwd<T, 2>(gy, y, scale, gx, gres, N, C, HW, relu, st);
-    default: return launch_bwd<T, 1>(gy, y, scale, gx, gres, N, C, HW, relu, st);
-  }
+  return dispatch_vec<T>(pick_vec<T>(HW, {gy, y, gx, gres}), [&](auto vc) {
+    constexpr int V = decltype(vc)::value;
+    const dim3 grid = plane_grid(N, C, HW / V);
+    return dispatch_bools(relu, gres != nullptr, [&](auto r, auto s) {
+      hipLaunchKernelGGL((frozen_bn_bwd_kernel<T, V, decltype(r)::value, decltype(s)::value>), grid, dim3(kThreads), 0, st,
+                         gp, yp, scale, xp, rp, C, HW);
+      return launch_status();
+    });
+  });
 }
 
 // channels-last: V | C (so a vector never straddles a pixel) and every base pointer V-aligned
-template <typename T> int pick_vec_nhwc(int C, const void* a, const void* b, const void* c, const void* d) {
-  return pick_vec<T>(C, a, b, c, d);
+template <typename T>
+int launch_fwd_nhwc(const void* x, const float* scale, const float* bias, const void* res, void* y, int64_t n, int C,
+                    int relu, hipStream_t st) {
+  const T* xp = static_cast<const T*>(x);
+  const T* rp = static_cast<const T*>(res);
+  T* yp = static_cast<T*>(y);
+  return dispatch_vec<T>(pick_vec<T>(C, {x, res, y}), [&](auto vc) {
+    constexpr int V = decltype(vc)::value;
+    const int64_t nvec = n / V;
+    const dim3 grid(nhwc_grid(nvec, C, V));
+    return dispatch_bools(relu, res != nullptr, [&](auto r, auto s) {
+      hipLaunchKernelGGL((frozen_bn_fwd_nhwc_kernel<T, V, decltype(r)::value, decltype(s)::value>), grid, dim3(kThreads), 0,
+                         st, xp, scale, bias, rp, yp, C, nvec);
+      return launch_status();
+    });
+  });
 }
 
 template <typename T>
-int dispatch_fwd_nhwc(const void* x, const float* scale, const float* bias, const void* res, void* y, int64_t n, int C,
-                      int relu, hipStream_t st) {
-  switch (pick_vec_nhwc<T>(C, x, res, y, nullptr)) {
-    case 8: return launch_fwd_nhwc<T, 8>(x, scale, bias, res, y, n, C, relu, st);
-    case 4: return launch_fwd_nhwc<T, 4>(x, scale, bias, res, y, n, C, relu, st);
-    case 2: return launch_fwd_nhwc<T, 2>(x, scale, bias, res, y, n, C, relu, st);
-    default: return launch_fwd_nhwc<T, 1>(x, scale, bias, res, y, n, C, relu, st);
-  }
-}
-
-template <typename T>
-int dispatch_bwd_nhwc(const void* gy, const void* y, const float* scale, void* gx, void* gres, int64_t n, int C, int relu,
-                      hipStream_t st) {
-  switch (pick_vec_nhwc<T>(C, gy, y, gx, gres)) {
-    case 8: return launch_bwd_nhwc<T, 8>(gy, y, scale, gx, gres, n, C, relu, st);
-    case 4: return launch_bwd_nhwc<T, 4>(gy, y, scale, gx, gres, n, C, relu, st);
-    case 2: return launch_bwd_nhwc<T, 2>(gy, y, scale, gx, gres, n, C, relu, st);
-    default: return launch_bwd_nhwc<T, 1>(gy, y, scale, gx, gres, n, C, relu, st);
-  }
+int launch_bwd_nhwc(const void* gy, const void* y, const float* scale, void* gx, void* gres, int64_t n, int C, int relu,
+                    hipStream_t st) {
+  const T* gp = static_cast<const T*>(gy);
+  const T* yp = static_cast<const T*>(y);
+  T* xp = static_cast<T*>(gx);
+  T* rp = static_cast<T*>(gres);
+  return dispatch_vec<T>(pick_vec<T>(C, {gy, y, gx, gres}), [&](auto vc) {
+    constexpr int V = decltype(vc)::value;
+    const int64_t nvec = n / V;
+    const dim3 grid(nhwc_grid(nvec, C, V));
+    return dispatch_bools(relu, gres != nullptr, [&](auto r, auto s) {
+      hipLaunchKernelGGL((frozen_bn_bwd_nhwc_kernel<T, V, decltype(r)::value, decltype(s)::value>), grid, dim3(kThreads), 0,
+                         st, gp, yp, scale, xp, rp, C, nvec);
+      return launch_status();
+    });
+  });
 }
 
 }  // namespace
@@ -319,12 +261,9 @@ DETOPS_API int detops_frozen_bn_act_forward(const void* x, const float* scale, c
   if (!x || !scale || !bias || !y) return DETOPS_EINVAL;
   if (static_cast<int64_t>(N) * C > 0x7fffffff / 2) return DETOPS_EUNSUPPORTED;
   hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case DETOPS_F32: return dispatch_fwd<float>(x, scale, bias, residual, y, N, C, HW, relu, st);
-    case DETOPS_F16: return dispatch_fwd<__half>(x, scale, bias, residual, y, N, C, HW, relu, st);
-    case DETOPS_BF16: return dispatch_fwd<__hip_bfloat16>(x, scale, bias, residual, y, N, C, HW, relu, st);
-    default: return DETOPS_EUNSUPPORTED;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return launch_fwd<typename decltype(tag)::type>(x, scale, bias, residual, y, N, C, HW, relu, st);
+  });
 }
 
 DETOPS_API int detops_frozen_bn_act_backward(const void* grad_y, const void* y, const float* scale, void* grad_x,
@@ -335,12 +274,9 @@ DETOPS_API int detops_frozen_bn_act_backward(const void* grad_y, const void* y, 
   if (!grad_y || !scale || !grad_x || (relu && !y)) return DETOPS_EINVAL;
   if (static_cast<int64_t>(N) * C > 0x7fffffff / 2) return DETOPS_EUNSUPPORTED;
   hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case DETOPS_F32: return dispatch_bwd<float>(grad_y, y, scale, grad_x, grad_residual, N, C, HW, relu, st);
-    case DETOPS_F16: return dispatch_bwd<__half>(grad_y, y, scale, grad_x, grad_residual, N, C, HW, relu, st);
-    case DETOPS_BF16: return dispatch_bwd<__hip_bfloat16>(grad_y, y, scale, grad_x, grad_residual, N, C, HW, relu, st);
-    default: return DETOPS_EUNSUPPORTED;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return launch_bwd<typename decltype(tag)::type>(grad_y, y, scale, grad_x, grad_residual, N, C, HW, relu, st);
+  });
 }
 
 DETOPS_API int detops_frozen_bn_act_forward_nhwc(const void* x, const float* scale, const float* bias,
@@ -351,12 +287,9 @@ DETOPS_API int detops_frozen_bn_act_forward_nhwc(const void* x, const float* sca
   if (!x || !scale || !bias || !y) return DETOPS_EINVAL;
   hipStream_t st = as_stream(stream);
   const int64_t n = rows * C;
-  switch (dtype) {
-    case DETOPS_F32: return dispatch_fwd_nhwc<float>(x, scale, bias, residual, y, n, C, relu, st);
-    case DETOPS_F16: return dispatch_fwd_nhwc<__half>(x, scale, bias, residual, y, n, C, relu, st);
-    case DETOPS_BF16: return dispatch_fwd_nhwc<__hip_bfloat16>(x, scale, bias, residual, y, n, C, relu, st);
-    default: return DETOPS_EUNSUPPORTED;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return launch_fwd_nhwc<typename decltype(tag)::type>(x, scale, bias, residual, y, n, C, relu, st);
+  });
 }
 
 DETOPS_API int detops_frozen_bn_act_backward_nhwc(const void* grad_y, const void* y, const float* scale, void* grad_x,
@@ -367,10 +300,7 @@ DETOPS_API int detops_frozen_bn_act_backward_nhwc(const void* grad_y, const void
   if (!grad_y || !scale || !grad_x || (relu && !y)) return DETOPS_EINVAL;
   hipStream_t st = as_stream(stream);
   const int64_t n = rows * C;
-  switch (dtype) {
-    case DETOPS_F32: return dispatch_bwd_nhwc<float>(grad_y, y, scale, grad_x, grad_residual, n, C, relu, st);
-    case DETOPS_F16: return dispatch_bwd_nhwc<__half>(grad_y, y, scale, grad_x, grad_residual, n, C, relu, st);
-    case DETOPS_BF16: return dispatch_bwd_nhwc<__hip_bfloat16>(grad_y, y, scale, grad_x, grad_residual, n, C, relu, st);
-    default: return DETOPS_EUNSUPPORTED;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return launch_bwd_nhwc<typename decltype(tag)::type>(grad_y, y, scale, grad_x, grad_residual, n, C, relu, st);
+  });
 }

@@ -14,24 +14,12 @@
 // vector itself — it is a few KB and spares a counting launch.  Sums are formed in a fixed order: bit-reproducible.
 #include <cmath>
 
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
-  return __shfl(v, 0);
-}
-
-__device__ __forceinline__ float wave_max_all(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off));
-  return __shfl(v, 0);
-}
 
 // #labels with lo <= label < hi — the SAME predicate the loss rows use, so that a malformed label (>= #classes) drops out
 // of the sum and of its normaliser alike; counted by the whole workgroup (every thread returns the count)
@@ -39,7 +27,7 @@ __device__ __forceinline__ float block_count_in(const int64_t* __restrict__ labe
                                                 float* s_red) {
   float c = 0.f;
   for (int i = threadIdx.x; i < n; i += kBlock) c += (labels[i] >= lo && labels[i] < hi) ? 1.f : 0.f;
-  c = wave_sum(c);
+  c = wave_sum_all(c);
   if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = c;
   __syncthreads();
   float t = 0.f;
@@ -71,7 +59,7 @@ fastrcnn_loss_kernel(const float* __restrict__ logits, const float* __restrict__
     m = wave_max_all(m);
     float s = 0.f;
     for (int c = lane; c < C; c += kWave) s += expf(x[c] - m);
-    s = wave_sum(s);
+    s = wave_sum_all(s);
     const float lse = logf(s);
     ce = (m + lse) - x[label];                      // -log_softmax(x)[label]
     for (int c = lane; c < C; c += kWave) gl[c] = (expf(x[c] - m - lse) - (c == label ? 1.f : 0.f)) * inv;
@@ -90,7 +78,7 @@ fastrcnn_loss_kernel(const float* __restrict__ logits, const float* __restrict__
     }
     gb[c] = g * inv;
   }
-  l1 = wave_sum(l1);
+  l1 = wave_sum_all(l1);
   if (lane == 0) { partial[2 * r] = ce; partial[2 * r + 1] = l1; }
 }
 
@@ -105,9 +93,7 @@ head_loss_finish_kernel(const float* __restrict__ partial, int rows, int width, 
   for (int i = threadIdx.x; i < rows; i += kBlock)
     for (int k = 0; k < width; ++k) v[k] += partial[i * width + k];
   for (int k = 0; k < 2; ++k) {
-    float w = v[k];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) w += __shfl_down(w, off);
+    const float w = wave_sum(v[k]);
     if ((threadIdx.x & (kWave - 1)) == 0) s_sum[k][threadIdx.x / kWave] = w;
   }
   __syncthreads();
@@ -149,7 +135,7 @@ mask_loss_kernel(const float* __restrict__ logits, const int64_t* __restrict__ l
     }
   }
   if (static_cast<int>(blockIdx.y) != own % kMaskSplit) return;      // one workgroup per ROI reports (0 for a non-positive)
-  loss = wave_sum(loss);
+  loss = wave_sum_all(loss);
   if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = loss;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -19,7 +19,7 @@
 
 #include <cmath>
 
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -40,12 +40,6 @@ __device__ __forceinline__ float iou_ref(const float4 g, float area_g, const flo
 __device__ __forceinline__ float box_area(const float4 b) {
 #pragma clang fp contract(off)
   return (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off));
-  return v;
 }
 
 // PASS = 0: per box the best ground truth (first index among ties, like torch.max on the CPU) and its IoU;

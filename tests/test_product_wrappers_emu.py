@@ -226,10 +226,12 @@ def test_fpn_topdown_equals_interpolate_plus_add(dtype, tol, shape):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("shape", [((2, 8, 10, 16), (5, 8)), ((1, 12, 7, 9), (4, 5)), ((2, 4, 13, 21), (7, 11)), ((1, 6, 6, 6), (6, 6))])
+@pytest.mark.parametrize("shape", [((2, 8, 10, 16), (5, 8)), ((1, 12, 7, 9), (4, 5)), ((2, 4, 13, 21), (7, 11)), ((1, 6, 6, 6), (6, 6)),
+                                   ((1, 3, 5, 12), (3, 6))])
 def test_fpn_topdown_channels_last_is_bit_equal_to_the_nchw_kernels(dtype, shape):
     """a channels-last lateral takes the NHWC kernels (detops_fpn_topdown_*_nhwc) and returns channels-last tensors; values and
-    both gradients are bit-equal to the NCHW kernels' (same arithmetic, same summation order)"""
+    both gradients are bit-equal to the NCHW kernels' (same arithmetic, same summation order); C = 3, W = 12 is width 1 of the
+    channels-last kernels and width 4 of the NCHW forward in every storage type"""
     from maskrcnn_benchmark import _C
     (N, C, H, W), (h, w) = shape
     g = torch.Generator().manual_seed(H * W + h + C)
@@ -250,11 +252,12 @@ def test_fpn_topdown_channels_last_is_bit_equal_to_the_nchw_kernels(dtype, shape
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("C,H,W", [(8, 9, 11), (12, 5, 7), (64, 6, 10), (3, 4, 5), (2048, 2, 3)])
+@pytest.mark.parametrize("C,H,W", [(8, 9, 11), (12, 5, 7), (64, 6, 10), (3, 4, 5), (2048, 2, 3), (4, 4, 4), (6, 3, 5)])
 @pytest.mark.parametrize("relu,res", [(False, False), (True, False), (True, True), (False, True)])
 def test_frozen_bn_channels_last_is_bit_equal_to_the_nchw_kernels(dtype, C, H, W, relu, res):
     """FrozenBatchNorm2d.fused on a channels-last activation: NHWC kernels, channels-last output and gradients, bit-equal to the
-    NCHW kernels (vector widths 1-8, channel counts that are / are not powers of two, C larger than a block's span)"""
+    NCHW kernels (vector widths 1-8, channel counts that are / are not powers of two, C larger than a block's span; (4, 4, 4)
+    is the NCHW kernels' width 8 for the half types, (6, 3, 5) the channels-last kernels' width 2)"""
     from maskrcnn_benchmark import _C
     from maskrcnn_benchmark.layers import FrozenBatchNorm2d
     rng = np.random.RandomState(C + H)
