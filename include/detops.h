@@ -561,6 +561,48 @@ int detops_keypoint_loss_f32(const float* logits, const int64_t* logit_strides, 
 int detops_heatmaps_to_keypoints_f32(const float* heatmaps, const int64_t* strides, const float* boxes, int N, int K, int H,
                                      int W, float* keypoints, float* scores, detops_stream_t stream);
 
+/* ---- masks at inference (csrc/masker.hip) ------------------------------------------------------------------------------
+ * detops_paste_masks — Masker / paste_mask_in_image (reference roi_heads/mask_head/inference.py:91-199) for every detection
+ *   of every image of the batch in one launch.  masks [N, M, M] contiguous (each detection's class channel), dtype code
+ *   DETOPS_F32 / F16 / BF16 with fp32 arithmetic (the reference casts to float); boxes [N, 4] fp32 xyxy; det_hw [N, 2]
+ *   int32 = (H, W) of the detection's image (the images of a batch differ); out_offset [N] int64 = where detection n's
+ *   H x W uint8 plane starts in `out` (bytes, any alignment; 64-bit address arithmetic).  Per detection:
+ *     - the map is zero-padded by `padding`; scale = (M + 2 * padding) / M as a Python float, rounded to fp32 by the multiply;
+ *     - expand_boxes in fp32 (half sizes and centre, half sizes * scale, centre -+ half size: one rounding each), then the
+ *       conversion to int32 by TRUNCATION TOWARD ZERO, not floor: a left edge of -0.4 becomes 0;
+ *     - w = max(x2 - x1 + 1, 1), h likewise; the padded map is resized to h x w as ATen's CPU bilinear kernel does with
+ *       align_corners = False: source max((d + 0.5) * (float(in) / out) - 0.5, 0), upper index clamped to in - 1, value
+ *       hy0 * (wx0 * a + wx1 * b) + hy1 * (wx0 * c + wx1 * d), every operation one fp32 rounding (no contraction);
+ *     - pixel = value > threshold for threshold >= 0, value * 255 != 0 for threshold < 0 (the reference's debugging mode);
+ *     - the window [max(x1, 0), min(x2 + 1, W)) x [max(y1, 0), min(y2 + 1, H)) of it lands in an H x W plane of zeros.
+ *   The reference has no defined answer for a box whose expanded integer window misses the image (its slice bounds go
+ *   negative); THIS LIBRARY'S CHOICE is an all-zero plane.  NaN and coordinates beyond +-5e8 saturate and give that plane.
+ *   Every byte of every plane is written exactly once (0 or 1), nothing outside the planes.  DETOPS_EINVAL for
+ *   padding < 1 (the reference's expand_masks is not defined there) and for M + 2 * padding > 64; N == 0 is a no-op.
+ * detops_paste_masks_rle_count / _write — the same masks (the same per-pixel device function) as UNCOMPRESSED COCO RLE
+ *   without the planes: per detection the run lengths over the H x W plane in column-major order, alternating 0-runs and
+ *   1-runs and starting with a 0-run.  Canonical: only a detection's first count may be 0 (pixel (0, 0) set), the counts
+ *   sum to H * W, an all-zero plane is the single count H * W.  The work is proportional to the clipped windows.
+ *     _count: run_offset [N + 1] int64 (device) = exclusive sum of the detections' count numbers;
+ *     the caller reads run_offset[N] (the one host read of the path) and allocates counts [run_offset[N]] int32;
+ *     _write: fills counts; detection n's are counts[run_offset[n] .. run_offset[n + 1]).
+ *   Both calls take the same arguments and the same workspace of detops_paste_masks_rle_workspace_bytes(N, max_w) bytes,
+ *   untouched in between; H * W of a detection must stay below 2^31.  max_w must be at least every W of det_hw: the
+ *   widths live on the device, so a smaller max_w cannot be refused — such a detection's window is silently CLIPPED to
+ *   the columns below max_w (its counts then still sum to H * W; nothing is written out of bounds).
+ *   Returns: DETOPS_EINVAL as detops_paste_masks, and for max_w < 1, max_w > 65535 * 32 (one workgroup row per 32
+ *   columns) or a null pointer; DETOPS_EWORKSPACE for a workspace smaller than the query's answer.  N == 0: _count
+ *   writes run_offset[0] = 0, _write is a no-op. */
+int detops_paste_masks(const void* masks, int dtype, const float* boxes, const int32_t* det_hw, const int64_t* out_offset,
+                       int N, int M, int padding, float threshold, unsigned char* out, detops_stream_t stream);
+size_t detops_paste_masks_rle_workspace_bytes(int N, int max_w);
+int detops_paste_masks_rle_count(const void* masks, int dtype, const float* boxes, const int32_t* det_hw, int N, int M,
+                                 int padding, float threshold, int max_w, int64_t* run_offset, void* workspace,
+                                 size_t workspace_bytes, detops_stream_t stream);
+int detops_paste_masks_rle_write(const void* masks, int dtype, const float* boxes, const int32_t* det_hw, int N, int M,
+                                 int padding, float threshold, int max_w, const int64_t* run_offset, int32_t* counts,
+                                 void* workspace, size_t workspace_bytes, detops_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused FrozenBatchNorm2d affine (+ residual) (+ ReLU) — the elementwise tail of every backbone
  * convolution: layers/batch_norm.py:19-31 (`x * scale + bias`), then `F.relu_`, and in the

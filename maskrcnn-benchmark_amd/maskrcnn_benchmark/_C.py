@@ -679,6 +679,86 @@ def heatmaps_to_keypoints(heatmaps, boxes):
     return kps, scores
 
 
+# ------------------------------------------------------------------------------------------ masks at inference
+def _paste_args(name, masks, boxes, sizes, counts):
+    """-> (masks [N,M,M] contiguous, boxes [N,4] fp32, per-image (H, W) list, per-image detection counts)"""
+    _need_cuda(name, masks, boxes)
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    if masks.dim() != 3 or masks.shape[1] != masks.shape[2]:
+        raise ValueError("%s: masks must be [N, 1, M, M] or [N, M, M], got %s" % (name, tuple(masks.shape)))
+    if masks.dtype not in _lib.DTYPE_CODE:
+        masks = masks.float()
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    counts = [1] * len(sizes) if counts is None else [int(c) for c in counts]
+    N = masks.shape[0]
+    if len(counts) != len(sizes) or sum(counts) != N or tuple(boxes.shape) != (N, 4) or min(counts, default=0) < 0 \
+            or any(h < 0 or w < 0 or h * w >= 2 ** 31 for h, w in sizes):
+        raise ValueError("%s: inconsistent arguments" % name)
+    return masks.contiguous(), _f32c(name, boxes), sizes, counts
+
+
+def _det_hw(sizes, counts, device):
+    hw = torch.tensor(sizes, dtype=torch.int32).reshape(-1, 2)
+    return hw.repeat_interleave(torch.tensor(counts, dtype=torch.int64), dim=0).to(device)
+
+
+def paste_masks(masks, boxes, sizes, threshold=0.5, padding=1, counts=None):
+    """Masker for every detection of a batch in one launch (extension; reference roi_heads/mask_head/inference.py:91-199,
+    include/detops.h: detops_paste_masks): masks [N,1,M,M] or [N,M,M] (fp32 / fp16 / bf16: each detection's class channel),
+    boxes [N,4] xyxy.  `sizes` lists (H, W) per detection, or per image together with `counts` (detections per image, in
+    order).  -> (flat uint8 buffer holding every plane, [views]): one bool view [n_i, 1, H_i, W_i] of the buffer per entry
+    of `sizes`."""
+    masks, boxes, sizes, counts = _paste_args("paste_masks", masks, boxes, sizes, counts)
+    N, M = masks.shape[0], masks.shape[1]
+    dev = masks.device
+    starts, offsets, end = [], [], 0
+    for (h, w), c in zip(sizes, counts):
+        starts.append(end)                   # planes back to back: the buffer holds nothing else
+        offsets.extend(end + k * h * w for k in range(c))
+        end += c * h * w
+    flat = torch.empty((end,), dtype=torch.uint8, device=dev)
+    if N:
+        det_hw = _det_hw(sizes, counts, dev)
+        out_offset = torch.tensor(offsets, dtype=torch.int64).to(dev)
+        with _on_device(masks), _timed(("paste_masks[N=%d,M=%d]", (N, M)), masks):
+            check(lib.detops_paste_masks(ptr(masks), _lib.DTYPE_CODE[masks.dtype], ptr(boxes), ptr(det_hw), ptr(out_offset),
+                                         N, M, int(padding), float(threshold), ptr(flat), stream_of(masks)), "paste_masks")
+    else:
+        check(lib.detops_paste_masks(None, 0, None, None, None, 0, max(M, 1), int(padding), float(threshold), None, None),
+              "paste_masks")
+    views = [flat[s:s + c * h * w].view(c, 1, h, w).view(torch.bool) for s, (h, w), c in zip(starts, sizes, counts)]
+    return flat, views
+
+
+def paste_masks_rle(masks, boxes, sizes, threshold=0.5, padding=1, counts=None):
+    """The masks of paste_masks as uncompressed COCO RLE, without the planes (extension; include/detops.h:
+    detops_paste_masks_rle_count / _write): -> (counts int32 [total], run_offset int64 [N + 1]), both on the device;
+    detection n's run lengths (column-major, starting with a 0-run) are counts[run_offset[n]:run_offset[n + 1]].  One host
+    read (the total) sizes `counts`."""
+    masks, boxes, sizes, per_image = _paste_args("paste_masks_rle", masks, boxes, sizes, counts)
+    N, M = masks.shape[0], masks.shape[1]
+    dev = masks.device
+    run_offset = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+    if N == 0:
+        return torch.empty((0,), dtype=torch.int32, device=dev), run_offset
+    det_hw = _det_hw(sizes, per_image, dev)
+    max_w = max(max(w for (_, w), c in zip(sizes, per_image) if c), 1)
+    nbytes = int(lib.detops_paste_masks_rle_workspace_bytes(N, max_w))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    args = (ptr(masks), _lib.DTYPE_CODE[masks.dtype], ptr(boxes), ptr(det_hw), N, M, int(padding), float(threshold), max_w)
+    with _on_device(masks):
+        with _timed(("paste_masks_rle_count[N=%d,M=%d]", (N, M)), masks):
+            check(lib.detops_paste_masks_rle_count(*args, ptr(run_offset), ptr(ws), nbytes, stream_of(masks)),
+                  "paste_masks_rle_count")
+        total = int(run_offset[-1].item())
+        out = torch.empty((total,), dtype=torch.int32, device=dev)
+        with _timed(("paste_masks_rle_write[N=%d,M=%d]", (N, M)), masks):
+            check(lib.detops_paste_masks_rle_write(*args, ptr(run_offset), ptr(out), ptr(ws), nbytes, stream_of(masks)),
+                  "paste_masks_rle_write")
+    return out, run_offset
+
+
 # ------------------------------------------------------------------------------------------ target assignment
 def match_boxes(gt_boxes, gt_valid, boxes, high_threshold, low_threshold, allow_low_quality_matches):
     """Fused IoU + Matcher (extension; reference structures/boxlist_ops.py:53-89 + modeling/matcher.py:42-112):

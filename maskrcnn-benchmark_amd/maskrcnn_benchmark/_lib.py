@@ -64,6 +64,10 @@ SIGNATURES = {
     "detops_keypoint_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "detops_keypoint_loss_f32": (c_int, [_P] * 4 + [c_int] * 4 + [_P] * 3 + [_P, c_size_t, _P]),
     "detops_heatmaps_to_keypoints_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 3),
+    "detops_paste_masks": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_float, _P, _P]),
+    "detops_paste_masks_rle_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "detops_paste_masks_rle_count": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, c_size_t, _P]),
+    "detops_paste_masks_rle_write": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_size_t, _P]),
     "detops_roi_align_fpn_forward_nhwc_workspace_bytes": (c_size_t, [c_int]),
     "detops_roi_align_fpn_forward_nhwc_f32": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P] + [c_int] * 8 + [c_float] * 3 + [_P, c_size_t, _P]),
     "detops_roi_align_fpn_backward_ring_nhwc_f32": (c_int, [_P] * 7 + [c_int] * 8 + [_P, c_size_t, _P]),

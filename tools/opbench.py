@@ -507,6 +507,35 @@ def bench_keypoint(C, iters):
     return out
 
 
+def bench_masker(C, iters):
+    """masks at inference (csrc/masker.hip): 100 detections of one 800 x 1333 image, M = 28, box sides log-uniform in
+    32-800 px.  Dense paste: bytes = the N * H * W planes written + the maps read (107 MB, ~17 us at the 6.29 TB/s copy
+    ceiling); the same detections as uncompressed RLE (count pass, scans, the host read of the total, write pass; bytes:
+    maps, column tables and counts — the planes are never stored); and paste_masks_torch on the same device tensors —
+    the per-detection loop of interpolate / threshold / slice assignment a user would write today."""
+    from maskrcnn_benchmark.modeling.roi_heads.mask_head.inference import paste_masks_torch
+    g = torch.Generator().manual_seed(5)
+    N, H, W, M = 100, 800, 1333, 28
+    s_ = torch.exp(torch.empty(N, 2).uniform_(np.log(32), np.log(800), generator=g))
+    xy = torch.rand(N, 2, generator=g) * torch.tensor([W - 32.0, H - 32.0])
+    boxes = torch.cat([xy, xy + s_], 1).cuda()
+    maps = torch.sigmoid(3 * torch.randn(N, 1, M, M, generator=g)).cuda()
+    alg = N * H * W + N * M * M * 4
+    window = (torch.minimum(xy + s_, torch.tensor([float(W), float(H)])) - xy).prod(1)
+    extra = {"window_px_mean": int(window.mean())}
+    out = []
+    us = dev_time_us(lambda: C.paste_masks(maps, boxes, [(H, W)], 0.5, 1, counts=[N]), iters)
+    out.append(_entry("paste_masks dense N=100 800x1333 M=28", us, alg, dict(extra, frac_of_copy_peak=round(alg / us / 1e3 / 6290.0, 4))))
+    us = dev_time_us(lambda: C.paste_masks_rle(maps, boxes, [(H, W)], 0.5, 1, counts=[N]), iters)
+    runs = int(C.paste_masks_rle(maps, boxes, [(H, W)], 0.5, 1, counts=[N])[1][-1])
+    # bytes this path touches: the maps read by both passes, the column tables written, scanned and read, the counts
+    rle_bytes = 2 * N * M * M * 4 + 3 * 2 * N * W * 4 + runs * 4
+    out.append(_entry("paste_masks_rle N=100 800x1333 M=28", us, rle_bytes, dict(extra, runs=runs)))
+    us = dev_time_us(lambda: paste_masks_torch(maps, boxes, H, W, 0.5, 1), max(3, iters // 10), warmup=2)
+    out.append(_entry("paste_masks_torch loop, device tensors N=100 800x1333 M=28", us, alg, extra))
+    return out
+
+
 def copy_ceiling(iters):
     a = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
     b = torch.empty_like(a)
@@ -566,6 +595,8 @@ def main():
         res += bench_targets(C, args.iters)
     if not only or "keypoint" in only:
         res += bench_keypoint(C, args.iters)
+    if not only or "masker" in only:
+        res += bench_masker(C, args.iters)
     if not only or "frozen_bn" in only:
         res += bench_frozen_bn(C, args.iters)
     if not only or "focal" in only:
