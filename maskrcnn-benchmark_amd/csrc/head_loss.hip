@@ -66,7 +66,8 @@ fastrcnn_loss_kernel(const float* __restrict__ logits, const float* __restrict__
   } else {
     for (int c = lane; c < C; c += kWave) gl[c] = 0.f;
   }
-  const int col0 = (label > 0) ? (agnostic ? 4 : 4 * static_cast<int>(label)) : -1;
+  // (label < C: a malformed label must not regress class-agnostic columns 4..7 while the normaliser leaves its row out)
+  const int col0 = (label > 0 && label < C) ? (agnostic ? 4 : 4 * static_cast<int>(label)) : -1;
   float l1 = 0.f;
   for (int c = lane; c < D; c += kWave) {
     float g = 0.f;

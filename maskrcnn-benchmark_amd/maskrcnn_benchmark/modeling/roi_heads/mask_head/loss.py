@@ -90,7 +90,7 @@ class MaskRCNNLossComputation(object):
             return mask_logits.sum() * 0
         from ..box_head import loss as box_loss
         if box_loss._FUSED_LOSS and _C.on_device(mask_logits):
-            # value + gradient in one pass (csrc/head_loss.hip; opt-in, see box_head/loss.py)
+            # value + gradient in one pass (csrc/head_loss.hip; the default, DETOPS_HEAD_LOSS=torch switches it off: see box_head/loss.py)
             return _C.mask_loss(mask_logits.float(), labels, mask_targets)
         # the class plane of every ROI by gather (reference: mask_logits[positive_inds, labels_pos], loss.py:137-139): its
         # backward is a scatter, where advanced indexing's is a sort-based index_put that leaves the device idle for

@@ -181,7 +181,7 @@ def test_tiny_mask_rcnn_trains_through_the_device_branches(monkeypatch):
 
 @pytest.mark.parametrize("backend", ["emu-device", "emu-lib"])
 def test_tiny_mask_rcnn_with_the_fused_head_losses_equals_the_aten_losses(backend, monkeypatch):
-    """DETOPS_HEAD_LOSS=fused (opt-in): the value + gradient kernels of csrc/head_loss.hip in the detector — same losses
+    """DETOPS_HEAD_LOSS=fused (the default; "torch" keeps the ATen compositions): the value + gradient kernels of csrc/head_loss.hip in the detector — same losses
     and same parameter gradients as the ATen compositions (same weights, same batch, same sampler draws).
     "emu-lib": through the product's own `_C.fastrcnn_loss` / `_C.mask_loss` autograd functions (and every other `_C`
     wrapper of the model) over the emulation library."""
