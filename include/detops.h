@@ -604,6 +604,48 @@ int detops_paste_masks_rle_write(const void* masks, int dtype, const float* boxe
                                  void* workspace, size_t workspace_bytes, detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Polygon instance masks (extensions; the reference rasterises polygons one ROI at a time on the CPU through pycocotools:
+ * structures/segmentation_mask.py:273-335, roi_heads/mask_head/loss.py:11-42, "FIXME: CPU computation bottleneck").
+ *
+ * Packed polygons: verts [V, 2] fp32 (x, y); poly_offset [P + 1] int32: polygon p owns vertices
+ * [poly_offset[p], poly_offset[p + 1]); inst_offset [G + 1] int32: instance g owns polygons [inst_offset[g], inst_offset[g + 1]).
+ * Offsets are clamped to [0, V] and [0, P]: wrong ones give wrong pixels, never an access outside the arrays.
+ *
+ * THE DEFINITION of the fill of one polygon xy = [x0, y0, x1, y1, ...] (k >= 3 vertices) on an h x w grid is this
+ * restatement of pycocotools' polygon-to-RLE routine (rleFrPoly).  It has NOT been checked against pycocotools, which
+ * is not available where this library is built and tested.  All arithmetic fp64, every operation one rounding (no
+ * contraction), int() truncates toward zero:
+ *     x[j] = int(5 * xy[2j] + .5), y[j] = int(5 * xy[2j + 1] + .5), closed by x[k] = x[0], y[k] = y[0];
+ *     every edge (xs, ys) -> (xe, ye) is walked in unit steps of its major axis (x when |dx| >= |dy|), from the end with
+ *     the smaller major coordinate (a, b) towards the other, d = 0 .. |major difference|: the major coordinate is a + d
+ *     and the minor one int(b + ((b' - b) / |major difference|) * d + .5); an edge of zero length is its single point;
+ *     the points are emitted in the polygon's direction, (u, v) = (x, y) of the walk;
+ *     two consecutive points with different u give a crossing: xd = (min(u, u') + .5) / 5 - .5; it counts if xd is an
+ *     integer in [0, w - 1]; yd = (min(v, v') + .5) / 5 - .5 clamped to [0, h]; position = xd * h + ceil(yd);
+ *     pixel (row, col) is set iff the number of crossings at column-major positions <= col * h + row is odd.
+ * A position at row h is row 0 of the next column (for the last column it fills nothing).  An instance is the union
+ * (OR) of its polygons' fills; polygons of fewer than 3 vertices fill nothing.  Coordinates with |5 * v| > 5e8 and NaN
+ * saturate to +-5e8 (the literal routine has no defined answer there).
+ *
+ * detops_polygon_mask_targets — the mask head's targets for S slots of a batch in one launch.  Slot s: instance
+ *   slot_inst[s] (int64, global index into the packed batch; outside [0, G): an all-zero target), box boxes[s] fp32
+ *   xyxy, slot_wh[s] = (W, H) int32 of the slot's image.  PolygonInstance.crop + resize((M, M)), without rounding:
+ *     xmin = min(max(b0, 0), W - 1), xmax = max(min(max(b2, 0), W), xmin + 1) (fp64), likewise y;
+ *     every vertex becomes fp32(fp32(x - fp32(xmin)) * fp32(M / (xmax - xmin))), quotient in fp64; vertices are not clamped;
+ *   then the fill on the M x M grid.  out [S, M, M] fp32 of 0 / 1, row-major, every element written once.
+ *   DETOPS_EINVAL: M < 1, M > 256, a negative count, a null pointer with S > 0 (verts may be null when V == 0).
+ *   S == 0 is a no-op.  The work of a slot is (edges of its instance) x M, whatever the ratio of instance to box size.
+ * detops_polygons_to_masks — the dense planes of the G instances of one H x W image: out [G, H, W] uint8 of 0 / 1,
+ *   every byte written once, zeros included.  DETOPS_EINVAL: a negative count, H > 3584 (a strip of columns of the
+ *   plane lives in LDS as bits), G > 65535, a null pointer; G, H or W == 0 is a no-op.  G * H * W may exceed 2^31.
+ * ---------------------------------------------------------------------------------------- */
+int detops_polygon_mask_targets(const float* verts, const int32_t* poly_offset, const int32_t* inst_offset, int V, int P,
+                                int G, const int64_t* slot_inst, const float* boxes, const int32_t* slot_wh, int S, int M,
+                                float* out, detops_stream_t stream);
+int detops_polygons_to_masks(const float* verts, const int32_t* poly_offset, const int32_t* inst_offset, int V, int P, int G,
+                             int H, int W, unsigned char* out, detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused FrozenBatchNorm2d affine (+ residual) (+ ReLU) — the elementwise tail of every backbone
  * convolution: layers/batch_norm.py:19-31 (`x * scale + bias`), then `F.relu_`, and in the
  * bottleneck tail `out += identity; relu` (modeling/backbone/resnet.py:343-366).

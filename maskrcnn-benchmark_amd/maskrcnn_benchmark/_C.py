@@ -863,6 +863,63 @@ def mask_targets(masks, mask_index, boxes, discretization_size):
     return out
 
 
+def _packed_polygons(name, verts, poly_offset, inst_offset):
+    if verts.dtype != torch.float32 or poly_offset.dtype != torch.int32 or inst_offset.dtype != torch.int32 \
+            or verts.dim() != 2 or verts.shape[1] != 2 or poly_offset.numel() < 1 or inst_offset.numel() < 1:
+        raise ValueError("%s: expected verts [V, 2] float32, poly_offset [P + 1] int32, inst_offset [G + 1] int32" % name)
+    if not (verts.device == poly_offset.device == inst_offset.device):
+        raise RuntimeError("%s: the packed polygons must live on one device" % name)
+    return verts.contiguous(), poly_offset.contiguous(), inst_offset.contiguous()
+
+
+def polygon_mask_targets(verts, poly_offset, inst_offset, slot_inst, boxes, slot_wh, discretization_size):
+    """Mask-head targets from packed polygons (extension; include/detops.h: detops_polygon_mask_targets; reference
+    roi_heads/mask_head/loss.py:11-42 over PolygonInstance.crop / resize / convert_to_binarymask): slot_inst [S] int64 (global
+    instance index), boxes [S,4] xyxy, slot_wh [S,2] int32 = (W, H) of the slot's image -> [S,M,M] float32 of 0 / 1.  One
+    launch for the whole batch.  CPU tensors take the numpy implementation of the same definition (_polygon_cpu.py)."""
+    verts, poly_offset, inst_offset = _packed_polygons("polygon_mask_targets", verts, poly_offset, inst_offset)
+    boxes = _f32c("polygon_mask_targets", boxes)
+    slot_inst = slot_inst.to(torch.int64).contiguous()
+    slot_wh = slot_wh.to(torch.int32).contiguous()
+    S, M = boxes.size(0), int(discretization_size)
+    if tuple(boxes.shape) != (S, 4) or tuple(slot_inst.shape) != (S,) or tuple(slot_wh.shape) != (S, 2) or M < 1:
+        raise ValueError("polygon_mask_targets: inconsistent arguments")
+    tensors = (verts, poly_offset, inst_offset, slot_inst, boxes, slot_wh)
+    if not any(on_device(t) for t in tensors):
+        from . import _polygon_cpu
+
+        return torch.from_numpy(_polygon_cpu.polygon_mask_targets(*(t.numpy() for t in tensors), M))
+    _need_cuda("polygon_mask_targets", *tensors)
+    V, P, G = verts.shape[0], poly_offset.numel() - 1, inst_offset.numel() - 1
+    out = torch.empty((S, M, M), dtype=torch.float32, device=boxes.device)
+    if S:
+        with _on_device(boxes), _timed(("polygon_mask_targets[S=%d,M=%d]", (S, M)), boxes):
+            check(lib.detops_polygon_mask_targets(ptr(verts), ptr(poly_offset), ptr(inst_offset), V, P, G, ptr(slot_inst),
+                                                  ptr(boxes), ptr(slot_wh), S, M, ptr(out), stream_of(boxes)),
+                  "polygon_mask_targets")
+    return out
+
+
+def polygons_to_masks(verts, poly_offset, inst_offset, height, width):
+    """Dense planes of the instances of one image (extension; include/detops.h: detops_polygons_to_masks) -> [G,H,W] uint8
+    of 0 / 1 on the device of the packed polygons; CPU tensors take the numpy implementation of the same definition."""
+    verts, poly_offset, inst_offset = _packed_polygons("polygons_to_masks", verts, poly_offset, inst_offset)
+    H, W = int(height), int(width)
+    if H < 0 or W < 0:
+        raise ValueError("polygons_to_masks: negative image size")
+    if not on_device(verts):
+        from . import _polygon_cpu
+
+        return torch.from_numpy(_polygon_cpu.polygons_to_masks(verts.numpy(), poly_offset.numpy(), inst_offset.numpy(), H, W))
+    V, P, G = verts.shape[0], poly_offset.numel() - 1, inst_offset.numel() - 1
+    out = torch.empty((G, H, W), dtype=torch.uint8, device=verts.device)
+    if out.numel():
+        with _on_device(verts), _timed(("polygons_to_masks[G=%d]", (G,)), verts):
+            check(lib.detops_polygons_to_masks(ptr(verts), ptr(poly_offset), ptr(inst_offset), V, P, G, H, W, ptr(out),
+                                               stream_of(verts)), "polygons_to_masks")
+    return out
+
+
 def match_labels(matched, gt_labels=None, valid=None, dtype=torch.int64):
     """Matcher output [N,K] -> labels in one launch (extension; reference modeling/rpn/loss.py:70-88,
     roi_heads/box_head/loss.py:56-72): matched >= 0 -> gt_labels[n, matched] (1 when gt_labels is None), -1 -> 0,

@@ -6,7 +6,8 @@ data/transforms/build.py:5-42, data/collate_batch.py:5-20):
   image   float32 [3, H, W] (unit-variance noise), H x W = a COCO-like size after the
           min-800 / max-1333 resize (default 800 x 1333 -> padded to 800 x 1344 by the collator);
   target  BoxList (xyxy, size (W, H)) with fields "labels" int64 in 1..80 and "masks"
-          SegmentationMask (binary, filled ellipses inscribed in the boxes), 8-20 objects; with
+          SegmentationMask (binary, filled ellipses inscribed in the boxes; with mask_format="poly" the same ellipses as
+          polygons of 24-64 vertices, every fourth instance as two overlapping polygons), 8-20 objects; with
           `with_keypoints` also "keypoints" PersonKeypoints [n, 17, 3]: most points inside their box with
           v = 1 or 2, some unlabelled (v = 0, x = y = 0), a few just outside the box.
 
@@ -25,7 +26,9 @@ from maskrcnn_benchmark.structures.segmentation_mask import SegmentationMask
 
 class SyntheticCOCODataset(torch.utils.data.Dataset):
     def __init__(self, length=1024, height=800, width=1333, num_classes=81, min_objects=8, max_objects=20,
-                 with_masks=True, seed=0, pixel_std=1.0, with_keypoints=False):
+                 with_masks=True, seed=0, pixel_std=1.0, with_keypoints=False, mask_format="mask"):
+        assert mask_format in ("mask", "poly"), mask_format
+        self.mask_format = mask_format
         self.length, self.height, self.width = length, height, width
         self.num_classes = num_classes
         self.min_objects, self.max_objects = min_objects, max_objects
@@ -56,7 +59,9 @@ class SyntheticCOCODataset(torch.utils.data.Dataset):
         boxes = torch.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2 - 1, cy + bh / 2 - 1], dim=1)
         target = BoxList(boxes, (W, H), mode="xyxy")
         target.add_field("labels", torch.randint(1, self.num_classes, (n,), generator=g))
-        if self.with_masks:
+        if self.with_masks and self.mask_format == "poly":
+            target.add_field("masks", SegmentationMask(_ellipse_polygons(cx, cy, bw, bh, index), (W, H), mode="poly"))
+        elif self.with_masks:
             yy = torch.arange(H, dtype=torch.float32)[None, :, None]
             xx = torch.arange(W, dtype=torch.float32)[None, None, :]
             ell = (((xx - cx[:, None, None]) / (bw[:, None, None] / 2)) ** 2 +
@@ -67,6 +72,20 @@ class SyntheticCOCODataset(torch.utils.data.Dataset):
             target.add_field("keypoints", PersonKeypoints(_draw_keypoints(boxes, g), (W, H)))
         target = target.clip_to_image(remove_empty=True)
         return image, target, index
+
+
+def _ellipse_polygons(cx, cy, bw, bh, index):
+    """the ellipses inscribed in the boxes as polygon instances: 24-64 vertices (a fixed function of the sample and the
+    instance: no draw from the generator, so the other fields are those of the dense format); every fourth instance is two
+    overlapping ellipses (a flat one and a tall one)"""
+    out = []
+    for i in range(len(cx)):
+        k = 24 + (index * 7 + i * 13) % 41
+        a = torch.arange(k, dtype=torch.float32) * (2 * math.pi / k)
+        parts = [(0.5, 0.5)] if i % 4 != 3 else [(0.5, 0.3), (0.3, 0.5)]
+        out.append([torch.stack([cx[i] + fx * bw[i] * a.cos(), cy[i] + fy * bh[i] * a.sin()], dim=1).reshape(-1).tolist()
+                    for fx, fy in parts])
+    return out
 
 
 def _draw_keypoints(boxes, g, K=17):

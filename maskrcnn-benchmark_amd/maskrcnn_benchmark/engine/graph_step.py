@@ -39,6 +39,10 @@ def _target_tensors(t):
         v = t.extra_fields[k]
         if torch.is_tensor(v):
             out.append(v)
+        elif getattr(v, "mode", None) == "poly":
+            # polygons live on the host and are packed per step: a captured graph would replay the first batch's targets
+            raise TypeError("GraphedTrainStep: target field %r holds polygon masks (SegmentationMask mode='poly'), which a "
+                            "captured graph cannot refill; run the step eagerly or convert('mask') the targets" % k)
         elif hasattr(v, "instances") and hasattr(v.instances, "masks"):    # SegmentationMask(BinaryMaskList)
             out.append(v.instances.masks)
         elif hasattr(v, "masks") and torch.is_tensor(v.masks):

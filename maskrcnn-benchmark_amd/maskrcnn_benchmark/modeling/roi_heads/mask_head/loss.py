@@ -8,6 +8,10 @@ host->device copy of the result; "FIXME: CPU computation bottleneck").  `project
 here evaluates the same crop window and the same bilinear formula (torch's align_corners=False
 sampling: src = (dst + 0.5) * size/M - 0.5 clamped at 0, taps (i, min(i+1, size-1))) for all ROIs at
 once on the device with four gathers, never leaving the GPU.
+
+Polygon targets (`SegmentationMask(mode="poly")`): the target is the matched instance's polygons cropped to the UNROUNDED
+clamped ROI, scaled to M x M and rasterised there (structures/segmentation_mask.py: PolygonInstance.crop / resize;
+the fill of include/detops.h).  `project_polygons_on_boxes` does this for the slots of the whole batch in one call.
 """
 import torch
 from torch.nn import functional as F
@@ -64,6 +68,25 @@ def project_masks_on_boxes(masks, mask_index, boxes, discretization_size):
     return val
 
 
+def project_polygons_on_boxes(proposals, polygon_lists, discretization_size, device):
+    """proposals: per image the BoxList of mask-head slots (field matched_idxs), polygon_lists: per image the PolygonList of
+    its ground truth -> [sum P, M, M] float32 on `device`.  Host work: concatenating the lists' cached packed arrays and one
+    copy of them; no loop over ROIs."""
+    from maskrcnn_benchmark.structures.segmentation_mask import PolygonList
+
+    packed = PolygonList.pack(list(polygon_lists))
+    slot_inst, slot_wh = [], []
+    for p, polys, base in zip(proposals, polygon_lists, packed.inst_base):
+        idx = p.get_field("matched_idxs").clamp(min=0).to(torch.int64)
+        # an image without instances: index G (no instance) gives all-zero targets, as the dense branch does
+        slot_inst.append(idx + base if len(polys) else torch.full_like(idx, packed.G))
+        slot_wh.append(torch.tensor([int(polys.size[0]), int(polys.size[1])], dtype=torch.int32).expand(len(p), 2))
+    boxes = torch.cat([p.convert("xyxy").bbox for p in proposals], dim=0).to(device=device, dtype=torch.float32)
+    k = packed.to(device)
+    return _C.polygon_mask_targets(k.verts, k.poly_offset, k.inst_offset, torch.cat(slot_inst).to(device), boxes,
+                                   torch.cat(slot_wh).to(device), discretization_size)
+
+
 class MaskRCNNLossComputation(object):
     def __init__(self, proposal_matcher, discretization_size):
         self.proposal_matcher = proposal_matcher
@@ -74,6 +97,12 @@ class MaskRCNNLossComputation(object):
         mask_logits [sum P, C, M, M]."""
         dev = mask_logits.device
         labels = torch.cat([p.get_field("labels") for p in proposals], dim=0)
+        fields = [t.get_field("masks") for t in targets]
+        if any(getattr(m, "mode", "mask") == "poly" for m in fields):
+            if not all(getattr(m, "mode", "mask") == "poly" for m in fields):
+                raise ValueError("a batch mixes polygon and binary mask targets")
+            return self._loss(mask_logits, labels, project_polygons_on_boxes(
+                proposals, [m.instances for m in fields], self.discretization_size, dev))
         parts = []
         for p, t in zip(proposals, targets):  # per image: crop windows clamp to that image's size
             m = t.get_field("masks")
@@ -84,7 +113,9 @@ class MaskRCNNLossComputation(object):
                 continue
             parts.append(project_masks_on_boxes(m, p.get_field("matched_idxs").clamp(min=0),
                                                 p.convert("xyxy").bbox, self.discretization_size))
-        mask_targets = torch.cat(parts, dim=0)
+        return self._loss(mask_logits, labels, torch.cat(parts, dim=0))
+
+    def _loss(self, mask_logits, labels, mask_targets):
         pos = labels > 0
         if mask_targets.numel() == 0:
             return mask_logits.sum() * 0

@@ -536,6 +536,54 @@ def bench_masker(C, iters):
     return out
 
 
+def bench_polygons(C, iters):
+    """mask-head targets from polygons (csrc/polygon.hip) next to the dense path at the same slots: 20 instances of one
+    800 x 1333 image as polygons of 24-200 vertices (jittered ellipses, every fourth instance two overlapping ones), 256
+    slots with boxes jittered around their instances, M = 28.  polygon_mask_targets reads the packed polygons (bytes:
+    vertices + offsets + boxes + targets); mask_targets crops and resizes the instances' 800 x 1333 uint8 planes (bytes: the
+    box windows read + targets; the planes themselves, 21 MB, must first reach the device).  polygons_to_masks writes those
+    20 planes (bytes: the planes)."""
+    from maskrcnn_benchmark.structures.segmentation_mask import PolygonList
+    rng = np.random.RandomState(11)
+    G, S, H, W, M = 20, 256, 800, 1333, 28
+    insts, ext = [], []
+    for g in range(G):
+        hw_, hh_ = np.exp(rng.uniform(np.log(12), np.log(330), 2))
+        cx, cy = rng.uniform(hw_, W - hw_), rng.uniform(min(hh_, H / 2 - 1), max(H - hh_, H / 2 + 1))
+        polys = []
+        for fx, fy in ([(1.0, 1.0)] if g % 4 != 3 else [(1.0, 0.6), (0.6, 1.0)]):
+            k = int(rng.randint(24, 201))
+            a = np.arange(k) * (2 * np.pi / k)
+            r = 1 + 0.08 * rng.uniform(-1, 1, k)
+            polys.append(np.stack([cx + fx * hw_ * r * np.cos(a), cy + fy * hh_ * r * np.sin(a)], 1).reshape(-1).tolist())
+        insts.append(polys)
+        ext.append((cx - hw_, cy - hh_, cx + hw_, cy + hh_))
+    plist = PolygonList(insts, (W, H))
+    k = plist.packed().to("cuda")
+    inst = torch.from_numpy(rng.randint(0, G, S)).cuda()
+    e = np.array(ext)[inst.cpu().numpy()]
+    side = np.stack([e[:, 2] - e[:, 0], e[:, 3] - e[:, 1]] * 2, 1)
+    boxes_np = (e + rng.uniform(-0.2, 0.2, (S, 4)) * side).astype(np.float32)
+    boxes_np[:, 2:] = np.maximum(boxes_np[:, 2:], boxes_np[:, :2] + 1)
+    boxes = torch.from_numpy(boxes_np).cuda()
+    wh = torch.tensor([[W, H]], dtype=torch.int32).expand(S, 2).contiguous().cuda()
+    verts_total = int(k.V)
+    extra = {"vertices": verts_total, "vertices_per_instance_mean": round(verts_total / G, 1)}
+    out = []
+    us = dev_time_us(lambda: C.polygon_mask_targets(k.verts, k.poly_offset, k.inst_offset, inst, boxes, wh, M), iters)
+    out.append(_entry("polygon_mask_targets S=256 M=28 (20 instances, 24-200 vertices)", us,
+                      k.buffer.numel() * 4 + S * (16 + 8 + 8) + S * M * M * 4, extra))
+    us = dev_time_us(lambda: C.polygons_to_masks(k.verts, k.poly_offset, k.inst_offset, H, W), iters)
+    out.append(_entry("polygons_to_masks G=20 800x1333", us, G * H * W, dict(extra, frac_of_copy_peak=round(G * H * W / us / 1e3 / 6290.0, 4))))
+    masks = C.polygons_to_masks(k.verts, k.poly_offset, k.inst_offset, H, W)
+    cb = np.clip(np.round(boxes_np), 0, [W, H, W, H])
+    window = float((np.maximum(cb[:, 2] - cb[:, 0], 1) * np.maximum(cb[:, 3] - cb[:, 1], 1)).sum())
+    us = dev_time_us(lambda: C.mask_targets(masks, inst, boxes, M), iters)
+    out.append(_entry("mask_targets S=256 M=28 (dense 800x1333 uint8 planes, same slots)", us, int(window) + S * M * M * 4,
+                      {"planes_bytes": G * H * W, "polygons_bytes": k.buffer.numel() * 4}))
+    return out
+
+
 def copy_ceiling(iters):
     a = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
     b = torch.empty_like(a)
@@ -597,6 +645,8 @@ def main():
         res += bench_keypoint(C, args.iters)
     if not only or "masker" in only:
         res += bench_masker(C, args.iters)
+    if not only or "polygons" in only:
+        res += bench_polygons(C, args.iters)
     if not only or "frozen_bn" in only:
         res += bench_frozen_bn(C, args.iters)
     if not only or "focal" in only:
