@@ -36,6 +36,7 @@ extern "C" {
 #define DETOPS_EINVAL   (-1) /* bad shape / null pointer / negative size            */
 #define DETOPS_EWORKSPACE (-2) /* workspace too small (see *_workspace_bytes)       */
 #define DETOPS_EUNSUPPORTED (-3) /* configuration outside what the kernels implement */
+#define DETOPS_EGTCAP   (-4) /* detops_eval_match only: some problem has more than DETOPS_EVAL_MAX_GT ground truths */
 
 typedef void* detops_stream_t; /* hipStream_t */
 
@@ -644,6 +645,90 @@ int detops_polygon_mask_targets(const float* verts, const int32_t* poly_offset, 
                                 float* out, detops_stream_t stream);
 int detops_polygons_to_masks(const float* verts, const int32_t* poly_offset, const int32_t* inst_offset, int V, int P, int G,
                              int H, int W, unsigned char* out, detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Detection evaluation (csrc/evaluate.hip; extensions: the reference stores every prediction, pastes and RLE-encodes the
+ * masks on the CPU and hands them to pycocotools' COCOeval, data/datasets/evaluation/coco/coco_eval.py; its VOC
+ * evaluation is data/datasets/evaluation/voc/voc_eval.py).  Here the detections and the ground truth of a batch are
+ * matched on the device and only the match records are kept.
+ *
+ * The unit of work is a PROBLEM: the detections and the ground-truth instances of one (image, category) pair.  The
+ * caller sorts the detections by problem and, inside a problem, by score descending (a stable sort: ties keep their
+ * input order), and the ground truths by problem (input order inside).  dt_offset / gt_offset [P + 1] int32 delimit a
+ * problem's detections and ground truths in those sorted arrays; iou_offset [P + 1] int64 is the exclusive sum of
+ * D_p * G_p: the IoU matrix of problem p is D_p x G_p, row-major, at iou_offset[p]; total_pairs = iou_offset[P].  Every
+ * per-detection / per-ground-truth argument below is in sorted order.
+ *
+ * detops_mask_pack — uint8 / bool planes to row-major bit rows.  Plane n is H x W = plane_hw[n] (int32 pairs) and
+ *   starts plane_offset[n] bytes into `planes` (the planes of a batch differ in size); its rows of ceil(W / 64) 64-bit
+ *   words start at words[word_offset[n]] (bit b of word c of a row is pixel 64 c + b; non-zero bytes are set pixels; bits
+ *   at or beyond W are zero).  area [N] int32 receives the set-pixel count (H * W < 2^31), extent [N, 4] int32 the tight
+ *   extents (first row, last row, first word column, last word column), (H, -1, ceil(W / 64), -1) for an empty plane.
+ *   Counts and extents are combined with integer atomics: deterministic.  max_words: the largest H * ceil(W / 64) of
+ *   the call (sizes the grid; speed only).  Every word is written exactly once.
+ * detops_mask_pair_counts — counts [total_pairs] int32: for every (detection, ground truth) pair of every problem, the
+ *   pixels set in both planes: popcount of the AND over the words inside the intersection of the two extents.  Pairs
+ *   with disjoint extents read no plane; a pair whose planes differ in (H, W) gets -1 and reads none.  Every element
+ *   is written exactly once; no floating point.
+ * detops_eval_iou — iou [total_pairs] fp64, every element written once.  Boxes are fp32 xyxy [*, 4].  mode:
+ *   DETOPS_EVAL_COCO_SEGM  i / (area_d + area_g - i) from counts and the int32 areas, fp64; i / area_d for a crowd; a count
+ *                          that is not positive gives 0, the -1 of a pair of planes of different sizes included;
+ *   DETOPS_EVAL_COCO_BBOX  both boxes as BoxList.convert("xywh") makes them, fp32: w = (x2 - x1) + 1, h likewise; then fp64
+ *                          with no further + 1: iw = min(x_d + w_d, x_g + w_g) - max(x_d, x_g), ih likewise, 0 unless both
+ *                          are > 0; i = iw * ih; u = w_d h_d + w_g h_g - i, or w_d h_d for a crowd;
+ *   DETOPS_EVAL_VOC        the reference's formula: + 1 on x2 and y2 of both boxes (fp32), then boxlist_iou's fp32
+ *                          expression with TO_REMOVE = 1 (areas (x2 - x1 + 1)(y2 - y1 + 1), wh = max(rb - lt + 1, 0),
+ *                          inter / ((area_d + area_g) - inter)), widened to fp64; gt_crowd is not read.
+ *   A union of 0 gives IoU 0 in every mode.  pycocotools divides 0 by 0 there: the original has no defined answer for
+ *   that case, and 0 is THIS LIBRARY'S CHOICE.  No operation is contracted.
+ * detops_eval_match — greedy matching, one wave per problem.
+ *   COCO modes (SEGM and BBOX match alike): a lane is an (area range a, threshold t) pair, iou_thrs [T] and
+ *   area_rngs [A, 2] are fp64 INPUTS, A * T <= 4096.  Ground truth g is ignored in range a when gt_flag[g] (iscrowd), or
+ *   gt_area[g] < lo_a, or gt_area[g] > hi_a.  The lane visits the non-ignored ground truths first and the ignored ones
+ *   after, each group in input order, and for every detection d in score order runs
+ *       iou = min(t, 1 - 1e-10); m = -1
+ *       for g in visiting order:
+ *           if matched[g] and not iscrowd[g]: continue
+ *           if m > -1 and not ignored[m] and ignored[g]: break
+ *           if IoU[d, g] < iou: continue
+ *           iou = IoU[d, g]; m = g
+ *       if m > -1: dt_match[a, t, d] = m; dt_ignore[a, t, d] = ignored[m]; matched[m] = 1
+ *   a detection left unmatched is ignored when dt_area[d] lies outside [lo_a, hi_a].  Outputs: dt_match int32
+ *   [A, T, D_total] (ground-truth index inside the problem, or -1), dt_ignore uint8 [A, T, D_total], gt_ignore uint8
+ *   [A, G_total]; D_total = dt_offset[P] and G_total = gt_offset[P] are passed as host values (they size the outputs: a
+ *   problem whose offsets reach beyond them is skipped).
+ *   DETOPS_EVAL_VOC (calc_detection_voc_prec_rec): per detection g* = the first argmax of its IoU row; match 0 if that
+ *   IoU < iou_thrs[0] (or G_p == 0); else -1 if gt_flag[g*] (difficult); else 1 if g* was not selected before and 0 if it
+ *   was; g* is marked selected in the last two cases.  Output voc_match int8 [D_total]; areas and area_rngs are unused.
+ *   THE LARGEST G_p SERVED IS DETOPS_EVAL_MAX_GT (the lanes' matched sets are 64-bit registers up to 64 ground truths and
+ *   live in LDS above).  max_gt: the largest G_p of the call (host value; sizes LDS).  With max_gt above the cap the
+ *   launch still serves every problem within it, leaves the outputs of the others untouched and returns DETOPS_EGTCAP,
+ *   a code no other condition produces: the caller computes those problems on the host.
+ * DETOPS_EINVAL: negative sizes, an unknown mode, a null pointer the mode needs (detops_eval_match: per-detection arrays
+ * may be null only when D_total == 0, per-ground-truth arrays only when G_total == 0; iou is null when no problem has
+ * a pair, which the entry point cannot tell, so it is not checked).
+ * N, P or total_pairs == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+#define DETOPS_EVAL_COCO_SEGM 0
+#define DETOPS_EVAL_COCO_BBOX 1
+#define DETOPS_EVAL_VOC 2
+#define DETOPS_EVAL_MAX_GT 4096
+int detops_mask_pack(const unsigned char* planes, const int64_t* plane_offset, const int32_t* plane_hw, int N,
+                     int64_t max_words, const int64_t* word_offset, uint64_t* words, int32_t* area, int32_t* extent,
+                     detops_stream_t stream);
+int detops_mask_pair_counts(const uint64_t* dt_words, const int64_t* dt_word_offset, const int32_t* dt_hw,
+                            const int32_t* dt_extent, const uint64_t* gt_words, const int64_t* gt_word_offset,
+                            const int32_t* gt_hw, const int32_t* gt_extent, const int32_t* dt_offset, const int32_t* gt_offset,
+                            const int64_t* iou_offset, int P, int64_t total_pairs, int32_t* counts, detops_stream_t stream);
+int detops_eval_iou(int mode, const int32_t* counts, const int32_t* dt_area, const int32_t* gt_area, const float* dt_boxes,
+                    const float* gt_boxes, const unsigned char* gt_crowd, const int32_t* dt_offset, const int32_t* gt_offset,
+                    const int64_t* iou_offset, int P, int64_t total_pairs, double* iou, detops_stream_t stream);
+int detops_eval_match(int mode, const double* iou, const int32_t* dt_offset, const int32_t* gt_offset,
+                      const int64_t* iou_offset, int P, int64_t D_total, int64_t G_total, int max_gt, const double* dt_area,
+                      const double* gt_area,
+                      const unsigned char* gt_flag, const double* iou_thrs, int T, const double* area_rngs, int A,
+                      int32_t* dt_match, unsigned char* dt_ignore, unsigned char* gt_ignore, signed char* voc_match,
+                      detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused FrozenBatchNorm2d affine (+ residual) (+ ReLU) — the elementwise tail of every backbone

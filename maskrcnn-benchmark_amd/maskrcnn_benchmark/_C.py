@@ -21,9 +21,10 @@ for its CUDA-only operators, e.g. csrc/ROIAlign.h:44).
 import ctypes
 import os
 
+import numpy as np
 import torch
 
-from . import _lib
+from . import _eval_cpu, _lib
 from ._lib import check, lib, ptr, stream_of
 
 # ------------------------------------------------------------------------------------------ helpers
@@ -918,6 +919,216 @@ def polygons_to_masks(verts, poly_offset, inst_offset, height, width):
             check(lib.detops_polygons_to_masks(ptr(verts), ptr(poly_offset), ptr(inst_offset), V, P, G, H, W, ptr(out),
                                                stream_of(verts)), "polygons_to_masks")
     return out
+
+
+# ------------------------------------------------------------------------------------------ detection evaluation
+EVAL_COCO_SEGM, EVAL_COCO_BBOX, EVAL_VOC = 0, 1, 2
+EVAL_MAX_GT = _eval_cpu.MAX_GT        # DETOPS_EVAL_MAX_GT: the largest G_p detops_eval_match serves
+_EGTCAP = -4
+
+
+def _np(t):
+    return None if t is None else t.detach().cpu().numpy()
+
+
+def _problem_args(name, dt_offset, gt_offset, iou_offset):
+    if dt_offset.dtype != torch.int32 or gt_offset.dtype != torch.int32 or iou_offset.dtype != torch.int64 \
+            or not (dt_offset.numel() == gt_offset.numel() == iou_offset.numel() >= 1):
+        raise ValueError("%s: expected dt_offset / gt_offset [P + 1] int32 and iou_offset [P + 1] int64" % name)
+    return dt_offset.contiguous(), gt_offset.contiguous(), iou_offset.contiguous(), dt_offset.numel() - 1
+
+
+def mask_pack(planes):
+    """Bit rows, pixel counts and tight extents of uint8 / bool planes (extension; include/detops.h: detops_mask_pack).
+    planes: a tensor [n, H, W] or a list of such tensors (the images of a batch differ in size) -> (words int64 [total]: the
+    64-bit words, word_offset int64 [N], hw int32 [N, 2], area int32 [N], extent int32 [N, 4]).  One launch per tensor of
+    the list (tensors that are views of ONE buffer, as paste_masks returns them, share a launch); contiguous planes are read
+    in place.  The host builds the per-plane sizes and offsets and copies them to the device (three small copies, one more
+    per launch).  CPU tensors take the numpy implementation (_eval_cpu.py)."""
+    if isinstance(planes, torch.Tensor):
+        planes = [planes]
+    groups = []
+    for t in planes:
+        if t.dim() != 3 or t.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("mask_pack: planes must be [n, H, W] uint8 or bool, got %s %s" % (tuple(t.shape), t.dtype))
+        if t.shape[1] * t.shape[2] >= 2 ** 31:
+            raise ValueError("mask_pack: a plane must hold fewer than 2^31 pixels")
+        t = t.contiguous()
+        groups.append(t.view(torch.uint8) if t.dtype == torch.bool else t)
+    if not any(on_device(t) for t in groups):
+        from . import _eval_cpu
+
+        w, off, hw, area, ext = _eval_cpu.mask_pack([t.numpy() for t in groups])
+        return (torch.from_numpy(w.view(np.int64)), torch.from_numpy(off), torch.from_numpy(hw), torch.from_numpy(area),
+                torch.from_numpy(ext))
+    _need_cuda("mask_pack", *groups)
+    dev = groups[0].device
+    hw_l, off_l, base_l, total = [], [], [], 0
+    for t in groups:
+        n, H, W = t.shape
+        per = H * ((W + 63) // 64)
+        hw_l.extend([(H, W)] * n)
+        off_l.extend(total + k * per for k in range(n))
+        base_l.extend(t.data_ptr() + k * H * W for k in range(n))
+        total += n * per
+    N = len(hw_l)
+    words = torch.empty((total,), dtype=torch.int64, device=dev)
+    area = torch.empty((N,), dtype=torch.int32, device=dev)
+    extent = torch.empty((N, 4), dtype=torch.int32, device=dev)
+    hw = torch.tensor(hw_l, dtype=torch.int32).reshape(-1, 2).to(dev)
+    word_offset = torch.tensor(off_l, dtype=torch.int64).to(dev)
+    if N:
+        # one launch per underlying buffer: plane addresses are offsets from the buffer's first plane
+        runs, start = [], 0
+        stores = [t.untyped_storage().data_ptr() for t in groups for _ in range(t.shape[0])]
+        for k in range(1, N + 1):
+            if k == N or stores[k] != stores[start]:
+                runs.append((start, k))
+                start = k
+        with _on_device(groups[0]), _timed(("mask_pack[N=%d]", (N,)), groups[0]):
+            for a, b in runs:
+                base = min(base_l[a:b])
+                plane_offset = torch.tensor([v - base for v in base_l[a:b]], dtype=torch.int64).to(dev)
+                max_words = max(h * ((w + 63) // 64) for h, w in hw_l[a:b])
+                check(lib.detops_mask_pack(base, ptr(plane_offset), hw[a:b].data_ptr(), b - a, max_words,
+                                           word_offset[a:b].data_ptr(), ptr(words), area[a:b].data_ptr(),
+                                           extent[a:b].data_ptr(), stream_of(words)), "mask_pack")
+    return words, word_offset, hw, area, extent
+
+
+def mask_pair_counts(dt_pack, gt_pack, dt_offset, gt_offset, iou_offset, total_pairs):
+    """Pixels set in both planes of every (detection, ground truth) pair of every problem (extension; include/detops.h:
+    detops_mask_pair_counts).  dt_pack / gt_pack: (words, word_offset, hw, extent) with the per-plane arrays in SORTED
+    (problem) order -> int32 [total_pairs]."""
+    dt_offset, gt_offset, iou_offset, P = _problem_args("mask_pair_counts", dt_offset, gt_offset, iou_offset)
+    total_pairs = int(total_pairs)
+    dw, dwo, dhw, dex = (t.contiguous() for t in dt_pack)
+    gw, gwo, ghw, gex = (t.contiguous() for t in gt_pack)
+    tensors = (dw, dwo, dhw, dex, gw, gwo, ghw, gex, dt_offset, gt_offset, iou_offset)
+    if not any(on_device(t) for t in tensors):
+        from . import _eval_cpu
+
+        out = _eval_cpu.mask_pair_counts(dw.numpy().view(np.uint64), dwo.numpy(), dhw.numpy(), dex.numpy(),
+                                         gw.numpy().view(np.uint64), gwo.numpy(), ghw.numpy(), gex.numpy(), dt_offset.numpy(),
+                                         gt_offset.numpy(), iou_offset.numpy())
+        return torch.from_numpy(out)
+    _need_cuda("mask_pair_counts", *tensors)
+    if dwo.dtype != torch.int64 or gwo.dtype != torch.int64 or any(t.dtype != torch.int32 for t in (dhw, dex, ghw, gex)) \
+            or dw.dtype != torch.int64 or gw.dtype != torch.int64:
+        raise ValueError("mask_pair_counts: packs must come from mask_pack")
+    counts = torch.empty((total_pairs,), dtype=torch.int32, device=dt_offset.device)
+    if total_pairs:
+        with _on_device(counts), _timed(("mask_pair_counts[pairs=%d]", (total_pairs,)), counts):
+            check(lib.detops_mask_pair_counts(ptr(dw), ptr(dwo), ptr(dhw), ptr(dex), ptr(gw), ptr(gwo), ptr(ghw), ptr(gex),
+                                              ptr(dt_offset), ptr(gt_offset), ptr(iou_offset), P, total_pairs, ptr(counts),
+                                              stream_of(counts)), "mask_pair_counts")
+    return counts
+
+
+def eval_iou(mode, dt_offset, gt_offset, iou_offset, total_pairs, counts=None, dt_area=None, gt_area=None, dt_boxes=None,
+             gt_boxes=None, gt_crowd=None):
+    """The fp64 IoU matrices of every problem (extension; include/detops.h: detops_eval_iou).  EVAL_COCO_SEGM: counts
+    [total_pairs] int32 and int32 areas; EVAL_COCO_BBOX / EVAL_VOC: fp32 xyxy boxes; gt_crowd uint8 / bool (COCO modes).
+    Everything in sorted (problem) order -> float64 [total_pairs]."""
+    dt_offset, gt_offset, iou_offset, P = _problem_args("eval_iou", dt_offset, gt_offset, iou_offset)
+    total_pairs, mode = int(total_pairs), int(mode)
+    if mode == EVAL_COCO_SEGM:
+        counts, dt_area, gt_area = (t.to(torch.int32).contiguous() for t in (counts, dt_area, gt_area))
+        dt_boxes = gt_boxes = None
+    else:
+        dt_boxes, gt_boxes = (t.to(torch.float32).contiguous().reshape(-1, 4) for t in (dt_boxes, gt_boxes))
+        counts = dt_area = gt_area = None
+    if gt_crowd is not None:
+        gt_crowd = gt_crowd.to(torch.uint8).contiguous()
+    tensors = [t for t in (dt_offset, gt_offset, iou_offset, counts, dt_area, gt_area, dt_boxes, gt_boxes, gt_crowd)
+               if t is not None]
+    if not any(on_device(t) for t in tensors):
+        from . import _eval_cpu
+
+        return torch.from_numpy(_eval_cpu.eval_iou(mode, _np(counts), _np(dt_area), _np(gt_area), _np(dt_boxes), _np(gt_boxes),
+                                                   _np(gt_crowd), dt_offset.numpy(), gt_offset.numpy(), iou_offset.numpy()))
+    _need_cuda("eval_iou", *tensors)
+    if counts is not None and counts.numel() != total_pairs:
+        raise ValueError("eval_iou: counts must hold total_pairs elements")
+    iou = torch.empty((total_pairs,), dtype=torch.float64, device=dt_offset.device)
+    if total_pairs:
+        with _on_device(iou), _timed(("eval_iou[pairs=%d]", (total_pairs,)), iou):
+            check(lib.detops_eval_iou(mode, ptr(counts), ptr(dt_area), ptr(gt_area), ptr(dt_boxes), ptr(gt_boxes), ptr(gt_crowd),
+                                      ptr(dt_offset), ptr(gt_offset), ptr(iou_offset), P, total_pairs, ptr(iou), stream_of(iou)),
+                  "eval_iou")
+    return iou
+
+
+def eval_match(mode, iou, dt_offset, gt_offset, iou_offset, counts_host, gt_flag, iou_thrs, dt_area=None, gt_area=None,
+               area_rngs=None):
+    """Greedy matching of every problem (extension; include/detops.h: detops_eval_match).  counts_host = (D_total, G_total,
+    max G_p) as Python ints; gt_flag: iscrowd (COCO modes) or difficult (EVAL_VOC); iou_thrs [T] and area_rngs [A, 2]
+    float64.  COCO modes -> (dt_match int32 [A, T, D_total], dt_ignore uint8 [A, T, D_total], gt_ignore uint8 [A, G_total]);
+    EVAL_VOC -> match int8 [D_total].  Problems with more than EVAL_MAX_GT ground truths are computed on the host
+    (_eval_cpu.py) and patched into the device result."""
+    dt_offset, gt_offset, iou_offset, P = _problem_args("eval_match", dt_offset, gt_offset, iou_offset)
+    mode = int(mode)
+    D_total, G_total, max_gt = (int(v) for v in counts_host)
+    iou = iou.to(torch.float64).contiguous()
+    gt_flag = gt_flag.to(torch.uint8).contiguous()
+    iou_thrs = torch.as_tensor(iou_thrs, dtype=torch.float64).reshape(-1).contiguous()
+    coco = mode != EVAL_VOC
+    if coco:
+        area_rngs = torch.as_tensor(area_rngs, dtype=torch.float64).reshape(-1, 2).contiguous()
+        dt_area, gt_area = dt_area.to(torch.float64).contiguous(), gt_area.to(torch.float64).contiguous()
+        A, T = area_rngs.shape[0], iou_thrs.numel()
+        if dt_area.numel() != D_total or gt_area.numel() != G_total:
+            raise ValueError("eval_match: areas do not match the problem sizes")
+    else:
+        area_rngs = dt_area = gt_area = None
+    if gt_flag.numel() != G_total or iou_thrs.numel() < 1:
+        raise ValueError("eval_match: inconsistent arguments")
+    tensors = [iou, dt_offset, gt_offset, iou_offset, gt_flag] + ([dt_area, gt_area] if coco else [])
+    from . import _eval_cpu
+
+    def host(only=None):
+        return _eval_cpu.eval_match(mode, _np(iou), _np(dt_offset), _np(gt_offset), _np(iou_offset), _np(dt_area), _np(gt_area),
+                                    _np(gt_flag), iou_thrs.cpu().numpy(), None if area_rngs is None else area_rngs.cpu().numpy(),
+                                    only=only)
+
+    if not any(on_device(t) for t in tensors):
+        out = host()
+        return torch.from_numpy(out) if not coco else tuple(torch.from_numpy(o) for o in out)
+    _need_cuda("eval_match", *tensors)
+    dev = iou.device
+    iou_thrs = iou_thrs.to(dev)
+    if coco:
+        area_rngs = area_rngs.to(dev)
+        dtm = torch.full((A, T, D_total), -1, dtype=torch.int32, device=dev)
+        dti = torch.zeros((A, T, D_total), dtype=torch.uint8, device=dev)
+        gti = torch.zeros((A, G_total), dtype=torch.uint8, device=dev)
+        vm = None
+    else:
+        A = T = 0
+        dtm = dti = gti = None
+        vm = torch.zeros((D_total,), dtype=torch.int8, device=dev)
+    rc = 0
+    if P:
+        with _on_device(iou), _timed(("eval_match[P=%d]", (P,)), iou):
+            rc = lib.detops_eval_match(mode, ptr(iou), ptr(dt_offset), ptr(gt_offset), ptr(iou_offset), P, D_total, G_total, max_gt, ptr(dt_area),
+                                       ptr(gt_area), ptr(gt_flag), ptr(iou_thrs), T, ptr(area_rngs), A, ptr(dtm), ptr(dti),
+                                       ptr(gti), ptr(vm), stream_of(iou))
+        if rc != _EGTCAP:
+            check(rc, "eval_match")
+    if rc == _EGTCAP:       # the problems beyond the cap: numpy, patched in
+        g = gt_offset.cpu().numpy()
+        big = [p for p in range(P) if int(g[p + 1]) - int(g[p]) > EVAL_MAX_GT]
+        out = host(only=big)
+        d = dt_offset.cpu().numpy()
+        for p in big:
+            d0, d1, g0, g1 = int(d[p]), int(d[p + 1]), int(g[p]), int(g[p + 1])
+            if coco:
+                dtm[:, :, d0:d1] = torch.from_numpy(out[0][:, :, d0:d1]).to(dev)
+                dti[:, :, d0:d1] = torch.from_numpy(out[1][:, :, d0:d1]).to(dev)
+                gti[:, g0:g1] = torch.from_numpy(out[2][:, g0:g1]).to(dev)
+            else:
+                vm[d0:d1] = torch.from_numpy(out[d0:d1]).to(dev)
+    return (dtm, dti, gti) if coco else vm
 
 
 def match_labels(matched, gt_labels=None, valid=None, dtype=torch.int64):

@@ -1,0 +1,197 @@
+"""Host implementation of the detection-evaluation steps defined in include/detops.h ("Detection evaluation"), for CPU
+tensors and for the problems csrc/evaluate.hip does not serve (more than MAX_GT ground truths): numpy, the same four
+steps with the same arguments — mask_pack, mask_pair_counts, eval_iou, eval_match.
+
+A problem is the detections (score descending, ties in input order) and the ground truths of one (image, category) pair;
+dt_offset / gt_offset [P + 1] delimit them in the sorted arrays and iou_offset [P + 1] its D_p x G_p row-major IoU matrix.
+"""
+import numpy as np
+
+COCO_SEGM, COCO_BBOX, VOC = 0, 1, 2
+MAX_GT = 4096    # DETOPS_EVAL_MAX_GT
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], dtype=np.int64)
+
+
+def _popcount(words):
+    return int(_POP8[np.ascontiguousarray(words).view(np.uint8)].sum())
+
+
+def mask_pack(planes):
+    """planes: a list of [n_i, H_i, W_i] arrays (non-zero = set) -> (words uint64 [total], word_offset int64 [N],
+    hw int32 [N, 2], area int32 [N], extent int32 [N, 4]): rows of ceil(W / 64) words, bit b of word c = pixel 64 c + b;
+    extent = first / last non-empty row, first / last non-empty word column, (H, -1, ceil(W / 64), -1) when empty"""
+    words, offs, hw, area, extent = [], [], [], [], []
+    total = 0
+    shifts = np.arange(64, dtype=np.uint64)
+    for group in planes:
+        group = np.asarray(group)
+        n, H, W = group.shape
+        WW = (W + 63) // 64
+        for k in range(n):
+            bits = np.zeros((H, WW * 64), dtype=np.uint64)
+            bits[:, :W] = group[k] != 0
+            w = (bits.reshape(H, WW, 64) << shifts).sum(axis=2, dtype=np.uint64) if H and WW else np.zeros((H, WW), np.uint64)
+            rows, cols = np.nonzero(w.any(axis=1))[0], np.nonzero(w.any(axis=0))[0]
+            extent.append((rows[0], rows[-1], cols[0], cols[-1]) if rows.size else (H, -1, WW, -1))
+            area.append(int((group[k] != 0).sum()))
+            hw.append((H, W))
+            offs.append(total)
+            words.append(w.reshape(-1))
+            total += H * WW
+    return (np.concatenate(words) if words else np.zeros((0,), np.uint64), np.array(offs, np.int64).reshape(-1),
+            np.array(hw, np.int32).reshape(-1, 2), np.array(area, np.int32).reshape(-1),
+            np.array(extent, np.int32).reshape(-1, 4))
+
+
+def _pairs(dt_offset, gt_offset, iou_offset):
+    """-> (d, g) index arrays [total_pairs] into the sorted detections / ground truths"""
+    P = len(dt_offset) - 1
+    total = int(iou_offset[P]) if P >= 0 else 0
+    d, g = np.zeros((total,), np.int64), np.zeros((total,), np.int64)
+    for p in range(P):
+        d0, g0 = int(dt_offset[p]), int(gt_offset[p])
+        D, G = int(dt_offset[p + 1]) - d0, int(gt_offset[p + 1]) - g0
+        if D > 0 and G > 0:
+            o = int(iou_offset[p])
+            d[o:o + D * G] = d0 + np.repeat(np.arange(D), G)
+            g[o:o + D * G] = g0 + np.tile(np.arange(G), D)
+    return d, g
+
+
+def mask_pair_counts(dt_words, dt_word_offset, dt_hw, dt_extent, gt_words, gt_word_offset, gt_hw, gt_extent, dt_offset,
+                     gt_offset, iou_offset):
+    """-> counts int32 [total_pairs]: pixels set in both planes of every pair (-1 where the planes differ in size)"""
+    d_idx, g_idx = _pairs(dt_offset, gt_offset, iou_offset)
+    out = np.zeros((d_idx.size,), np.int32)
+    for i, (d, g) in enumerate(zip(d_idx, g_idx)):
+        H, W = int(dt_hw[d][0]), int(dt_hw[d][1])
+        if H != int(gt_hw[g][0]) or W != int(gt_hw[g][1]):
+            out[i] = -1
+            continue
+        WW = (W + 63) // 64
+        r0, r1 = max(int(dt_extent[d][0]), int(gt_extent[g][0])), min(int(dt_extent[d][1]), int(gt_extent[g][1]))
+        c0, c1 = max(int(dt_extent[d][2]), int(gt_extent[g][2])), min(int(dt_extent[d][3]), int(gt_extent[g][3]))
+        if r0 > r1 or c0 > c1:
+            continue
+        a = dt_words[int(dt_word_offset[d]):int(dt_word_offset[d]) + H * WW].reshape(H, WW)[r0:r1 + 1, c0:c1 + 1]
+        b = gt_words[int(gt_word_offset[g]):int(gt_word_offset[g]) + H * WW].reshape(H, WW)[r0:r1 + 1, c0:c1 + 1]
+        out[i] = _popcount(a & b)
+    return out
+
+
+def eval_iou(mode, counts, dt_area, gt_area, dt_boxes, gt_boxes, gt_crowd, dt_offset, gt_offset, iou_offset):
+    """-> iou float64 [total_pairs]; a union of 0 gives 0"""
+    d, g = _pairs(dt_offset, gt_offset, iou_offset)
+    if d.size == 0:
+        return np.zeros((0,), np.float64)
+    crowd = np.asarray(gt_crowd)[g] != 0 if gt_crowd is not None and mode != VOC else np.zeros(d.shape, bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if mode == COCO_SEGM:
+            i = np.asarray(counts).astype(np.float64)
+            da, ga = np.asarray(dt_area)[d].astype(np.float64), np.asarray(gt_area)[g].astype(np.float64)
+            u = np.where(crowd, da, (da + ga) - i)
+            return np.where((i > 0) & (u > 0), i / u, 0.0)
+        one = np.float32(1)
+        db, gb = np.asarray(dt_boxes, np.float32)[d], np.asarray(gt_boxes, np.float32)[g]
+        if mode == COCO_BBOX:
+            dw, dh = (db[:, 2] - db[:, 0]) + one, (db[:, 3] - db[:, 1]) + one        # BoxList.convert("xywh"), fp32
+            gw, gh = (gb[:, 2] - gb[:, 0]) + one, (gb[:, 3] - gb[:, 1]) + one
+            dx, dy, gx, gy = (v.astype(np.float64) for v in (db[:, 0], db[:, 1], gb[:, 0], gb[:, 1]))
+            dw, dh, gw, gh = (v.astype(np.float64) for v in (dw, dh, gw, gh))
+            da, ga = dw * dh, gw * gh
+            iw = np.minimum(dx + dw, gx + gw) - np.maximum(dx, gx)
+            ih = np.minimum(dy + dh, gy + gh) - np.maximum(dy, gy)
+            i = iw * ih
+            u = np.where(crowd, da, (da + ga) - i)
+            return np.where((iw > 0) & (ih > 0) & (u > 0), i / u, 0.0)
+        dx2, dy2, gx2, gy2 = db[:, 2] + one, db[:, 3] + one, gb[:, 2] + one, gb[:, 3] + one   # the evaluation's own + 1
+        area_d = ((dx2 - db[:, 0]) + one) * ((dy2 - db[:, 1]) + one)
+        area_g = ((gx2 - gb[:, 0]) + one) * ((gy2 - gb[:, 1]) + one)
+        w = np.maximum((np.minimum(dx2, gx2) - np.maximum(db[:, 0], gb[:, 0])) + one, np.float32(0))
+        h = np.maximum((np.minimum(dy2, gy2) - np.maximum(db[:, 1], gb[:, 1])) + one, np.float32(0))
+        inter = w * h
+        u = (area_d + area_g) - inter
+        assert inter.dtype == np.float32 and u.dtype == np.float32
+        return np.where(u != 0, inter / u, np.float32(0)).astype(np.float64)
+
+
+def _match_coco_problem(iou, dt_area, gt_area, crowd, iou_thrs, area_rngs):
+    """iou [D, G] -> dt_match int32 [A, T, D], dt_ignore uint8 [A, T, D], gt_ignore uint8 [A, G].  Per lane (a, t) the
+    walk of the definition keeps the last ground truth with the largest IoU >= the threshold among the non-ignored ones
+    not yet taken, else among the ignored ones not yet taken (crowds stay available)."""
+    D, G = iou.shape
+    A, T = area_rngs.shape[0], iou_thrs.shape[0]
+    lo, hi = area_rngs[:, 0], area_rngs[:, 1]
+    gt_ign = crowd[None, :] | (gt_area[None, :] < lo[:, None]) | (gt_area[None, :] > hi[:, None])       # [A, G]
+    ign = np.repeat(gt_ign, T, axis=0)                                                                    # [L, G]
+    thr = np.tile(np.minimum(iou_thrs, 1 - 1e-10), A)                                                     # [L]
+    L = A * T
+    taken = np.zeros((L, G), bool)
+    dtm = np.full((L, D), -1, np.int32)
+    dti = np.zeros((L, D), np.uint8)
+    d_out = (dt_area[None, :] < lo[:, None]) | (dt_area[None, :] > hi[:, None])                           # [A, D]
+    d_out = np.repeat(d_out, T, axis=0)
+    lanes = np.arange(L)
+    for d in range(D):
+        m = np.full((L,), -1, np.int64)
+        if G:
+            free = ~(taken & ~crowd[None, :])
+            for group in (~ign, ign):
+                v = np.where(free & group, iou[d][None, :], -np.inf)
+                last = G - 1 - np.argmax(v[:, ::-1], axis=1)             # the last index of the row maximum
+                found = (v[lanes, last] >= thr) & (m < 0)
+                m = np.where(found, last, m)
+            hit = m >= 0
+            taken[lanes[hit], m[hit]] = True
+            dti[hit, d] = ign[lanes[hit], m[hit]]
+        dtm[:, d] = m
+        miss = m < 0
+        dti[miss, d] = d_out[miss, d]
+    return dtm.reshape(A, T, D), dti.reshape(A, T, D), gt_ign.astype(np.uint8)
+
+
+def _match_voc_problem(iou, difficult, thresh):
+    D, G = iou.shape
+    out = np.zeros((D,), np.int8)
+    if G == 0:
+        return out
+    selected = np.zeros((G,), bool)
+    for d in range(D):
+        g = int(np.argmax(iou[d]))
+        if iou[d, g] < thresh:
+            continue
+        if difficult[g]:
+            out[d] = -1
+        else:
+            out[d] = 0 if selected[g] else 1
+        selected[g] = True
+    return out
+
+
+def eval_match(mode, iou, dt_offset, gt_offset, iou_offset, dt_area, gt_area, gt_flag, iou_thrs, area_rngs, only=None):
+    """COCO modes -> (dt_match int32 [A, T, D_total], dt_ignore uint8 [A, T, D_total], gt_ignore uint8 [A, G_total]);
+    VOC -> match int8 [D_total].  `only`: the problems to compute (the others' outputs stay -1 / 0)."""
+    P = len(dt_offset) - 1
+    D_total, G_total = int(dt_offset[P]), int(gt_offset[P])
+    iou_thrs = np.asarray(iou_thrs, np.float64).reshape(-1)
+    gt_flag = np.asarray(gt_flag) != 0
+    if mode == VOC:
+        out = np.zeros((D_total,), np.int8)
+    else:
+        area_rngs = np.asarray(area_rngs, np.float64).reshape(-1, 2)
+        A, T = area_rngs.shape[0], iou_thrs.shape[0]
+        dtm = np.full((A, T, D_total), -1, np.int32)
+        dti = np.zeros((A, T, D_total), np.uint8)
+        gti = np.zeros((A, G_total), np.uint8)
+    for p in (range(P) if only is None else only):
+        d0, d1, g0, g1 = int(dt_offset[p]), int(dt_offset[p + 1]), int(gt_offset[p]), int(gt_offset[p + 1])
+        o = int(iou_offset[p])
+        mat = np.asarray(iou[o:o + (d1 - d0) * (g1 - g0)], np.float64).reshape(d1 - d0, g1 - g0)
+        if mode == VOC:
+            out[d0:d1] = _match_voc_problem(mat, gt_flag[g0:g1], float(iou_thrs[0]))
+        else:
+            a, b, c = _match_coco_problem(mat, np.asarray(dt_area[d0:d1], np.float64), np.asarray(gt_area[g0:g1], np.float64),
+                                          gt_flag[g0:g1], iou_thrs, area_rngs)
+            dtm[:, :, d0:d1], dti[:, :, d0:d1], gti[:, g0:g1] = a, b, c
+    return out if mode == VOC else (dtm, dti, gti)

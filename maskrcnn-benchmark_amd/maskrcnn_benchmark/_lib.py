@@ -70,6 +70,11 @@ SIGNATURES = {
     "detops_paste_masks_rle_write": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_size_t, _P]),
     "detops_polygon_mask_targets": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
     "detops_polygons_to_masks": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P]),
+    "detops_mask_pack": (c_int, [_P, _P, _P, c_int, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    "detops_mask_pair_counts": (c_int, [_P] * 11 + [c_int, ctypes.c_int64, _P, _P]),
+    "detops_eval_iou": (c_int, [c_int] + [_P] * 9 + [c_int, ctypes.c_int64, _P, _P]),
+    "detops_eval_match": (c_int, [c_int] + [_P] * 4 + [c_int, ctypes.c_int64, ctypes.c_int64, c_int] + [_P] * 4
+                          + [c_int, _P, c_int] + [_P] * 5),
     "detops_roi_align_fpn_forward_nhwc_workspace_bytes": (c_size_t, [c_int]),
     "detops_roi_align_fpn_forward_nhwc_f32": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P] + [c_int] * 8 + [c_float] * 3 + [_P, c_size_t, _P]),
     "detops_roi_align_fpn_backward_ring_nhwc_f32": (c_int, [_P] * 7 + [c_int] * 8 + [_P, c_size_t, _P]),
@@ -147,7 +152,8 @@ SIGNATURES = {
 }
 
 _ERRORS = {-1: "DETOPS_EINVAL (bad shape / null pointer)", -2: "DETOPS_EWORKSPACE (workspace too small)",
-           -3: "DETOPS_EUNSUPPORTED (configuration not implemented)"}
+           -3: "DETOPS_EUNSUPPORTED (configuration not implemented)",
+           -4: "DETOPS_EGTCAP (a problem has more ground truths than detops_eval_match serves)"}
 
 
 def _load():

@@ -1,0 +1,143 @@
+"""Detection evaluation (reference data/datasets/evaluation/): `evaluate` dispatches on the dataset as the reference's
+does; COCO-shaped datasets go to the streaming COCO-style evaluator (coco_style.py), VOC-shaped ones to voc.py.
+
+Not built, and raising NotImplementedError: `box_only` (the AR of RPN proposals), the `keypoints` IoU type (OKS) and the
+Cityscapes evaluator.
+"""
+import logging
+import os
+from collections import OrderedDict
+
+import torch
+
+from .coco_style import COCOStyleEvaluator, STAT_NAMES
+from .voc import do_voc_evaluation, eval_detection_voc  # noqa: F401
+
+
+def dataset_style(dataset):
+    """"coco" | "voc" | "cityscapes" | None: the dataset's `evaluation_style` attribute; the synthetic COCO-shaped dataset is "coco" """
+    from maskrcnn_benchmark.data.synthetic import SyntheticCOCODataset
+
+    style = getattr(dataset, "evaluation_style", None)
+    if style is None and isinstance(dataset, SyntheticCOCODataset):
+        style = "coco"
+    return style
+
+
+def evaluate(dataset, predictions, output_folder, **kwargs):
+    """dataset: the dataset the predictions (a list of BoxList, one per image, in dataset order) were made on;
+    output_folder: where result files go (None: nowhere) -> the evaluation's result"""
+    args = dict(dataset=dataset, predictions=predictions, output_folder=output_folder, **kwargs)
+    style = dataset_style(dataset)
+    if style == "coco":
+        return coco_evaluation(**args)
+    if style == "voc":
+        return voc_evaluation(**args)
+    if style == "cityscapes":
+        raise NotImplementedError("the Cityscapes evaluator is not built")
+    raise NotImplementedError("Unsupported dataset type {}.".format(dataset.__class__.__name__))
+
+
+def check_scope(box_only, iou_types):
+    if box_only:
+        raise NotImplementedError("box_only (the AR of RPN proposals) is not built")
+    if "keypoints" in iou_types:
+        raise NotImplementedError("the keypoints IoU type (OKS) is not built")
+
+
+def _groundtruth(dataset, index):
+    return dataset.get_groundtruth(index) if hasattr(dataset, "get_groundtruth") else dataset[index][1]
+
+
+def coco_evaluation(dataset, predictions, output_folder, box_only=False, iou_types=("bbox",), expected_results=(),
+                    expected_results_sigma_tol=4, batch=8):
+    check_scope(box_only, iou_types)
+    num_classes = getattr(dataset, "num_classes", None) or 81
+    evaluator = COCOStyleEvaluator(iou_types, num_classes)
+    for i in range(0, len(predictions), batch):
+        preds = list(predictions[i:i + batch])
+        dev = preds[0].bbox.device
+        evaluator.update(preds, [_groundtruth(dataset, j).to(dev) for j in range(i, i + len(preds))])
+    return finish_coco(evaluator, output_folder, expected_results, expected_results_sigma_tol)
+
+
+def finish_coco(evaluator, output_folder=None, expected_results=(), expected_results_sigma_tol=4):
+    """summarize, log the table, check the expected results, save coco_results.pth -> COCOResults"""
+    logger = logging.getLogger("maskrcnn_benchmark.inference")
+    evaluator.summarize()
+    results = COCOResults(*evaluator.iou_types)
+    results.update(evaluator)
+    logger.info(results)
+    logger.info(format_stats(evaluator.stats))
+    check_expected_results(results, expected_results, expected_results_sigma_tol)
+    if output_folder:
+        torch.save(results, os.path.join(output_folder, "coco_results.pth"))
+        with open(os.path.join(output_folder, "coco_results.txt"), "w") as f:
+            f.write(repr(results) + format_stats(evaluator.stats))
+    return results
+
+
+def format_stats(stats):
+    """{iou type: the 12 numbers} -> the table as text"""
+    text = "\n"
+    for iou_type, s in stats.items():
+        text += "%s\n" % iou_type
+        text += "".join("  %-6s %8.4f\n" % (n, v) for n, v in zip(STAT_NAMES, s))
+    return text
+
+
+def voc_evaluation(dataset, predictions, output_folder, box_only=False, **_):
+    logger = logging.getLogger("maskrcnn_benchmark.inference")
+    if box_only:
+        logger.warning("voc evaluation doesn't support box_only, ignored.")
+    logger.info("performing voc evaluation, ignored iou_types.")
+    return do_voc_evaluation(dataset=dataset, predictions=predictions, output_folder=output_folder, logger=logger)
+
+
+_AP_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl")
+
+
+class COCOResults(object):
+    """The headline numbers per task, under the reference's names (its COCOResults): `results[task][metric]`, -1 until
+    filled; printed as a 'Task:' line, the metric names and the values to four decimals."""
+
+    METRICS = {
+        "bbox": list(_AP_NAMES),
+        "segm": list(_AP_NAMES),
+        "box_proposal": ["AR%s@%d" % (size, limit) for limit in (100, 1000) for size in ("", "s", "m", "l")],
+        "keypoints": [name for name in _AP_NAMES if name != "APs"],
+    }
+
+    def __init__(self, *iou_types):
+        unknown = [t for t in iou_types if t not in self.METRICS]
+        assert not unknown, unknown
+        self.results = OrderedDict()
+        for task in iou_types:
+            self.results[task] = OrderedDict.fromkeys(self.METRICS[task], -1)
+
+    def update(self, evaluator):
+        """evaluator: a summarized COCOStyleEvaluator (the reference takes a pycocotools COCOeval), or None"""
+        if evaluator is None:
+            return
+        assert isinstance(evaluator, COCOStyleEvaluator)
+        for task, stats in evaluator.stats.items():
+            self.results[task].update(zip(self.METRICS[task], (float(v) for v in stats)))
+
+    def __repr__(self):
+        lines = [""]
+        for task, metrics in self.results.items():
+            lines += ["Task: %s" % task, ", ".join(metrics), ", ".join("%.4f" % v for v in metrics.values())]
+        return "\n".join(lines) + "\n"
+
+
+def check_expected_results(results, expected_results, sigma_tol):
+    """expected_results: [(task, metric, (mean, std))].  A value strictly inside mean -+ sigma_tol * std is logged as PASS
+    (info), any other as FAIL (error), in the reference's wording; nothing is raised."""
+    logger = logging.getLogger("maskrcnn_benchmark.inference")
+    for task, metric, (mean, std) in expected_results or ():
+        value = results.results[task][metric]
+        half = sigma_tol * std
+        inside = mean - half < value < mean + half
+        text = "%s > %s sanity check (actual vs. expected): %.3f vs. mean=%.4f, std=%s, range=(%.4f, %.4f)" % (
+            task, metric, value, mean, "{:.4}".format(std), mean - half, mean + half)
+        logger.log(logging.INFO if inside else logging.ERROR, ("PASS: " if inside else "FAIL: ") + text)

@@ -1,0 +1,271 @@
+"""COCO-style detection evaluation as a streaming evaluator.
+
+Per batch the detections and the ground truth are matched where they live (on the device: csrc/evaluate.hip through
+maskrcnn_benchmark._C; CPU tensors: _eval_cpu.py) and only the match records are kept, a few KB per image; precision and
+recall are accumulated from them once, on the host, in fp64 numpy.
+
+The rules are a restatement of pycocotools.cocoeval (evaluateImg, accumulate, summarize) written from knowledge of that
+code.  It has NOT been checked against pycocotools, which is not available where this project is built and tested;
+tests/eval_refs.py is the literal, loop-by-loop form everything here is pinned to.
+"""
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from maskrcnn_benchmark import _C
+from maskrcnn_benchmark.structures.segmentation_mask import SegmentationMask
+
+IOU_THRS = np.linspace(0.5, 0.95, 10)
+REC_THRS = np.linspace(0.0, 1.0, 101)
+AREA_RNGS = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], dtype=np.float64)
+MAX_DETS = (1, 10, 100)
+STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
+
+
+def build_problems(dt_img, dt_label, dt_score, gt_img, gt_label, num_classes, max_dets=MAX_DETS[-1]):
+    """The (image, category) problems of a batch, with torch sorts on the tensors' device.
+    -> dict: dt_order / gt_order (indices into the inputs, sorted by problem; detections by score descending inside a
+    problem, ties in input order, at most `max_dets` per problem), dt_offset / gt_offset [P + 1] int32, iou_offset [P + 1]
+    int64 (device), and on the host: image / category [P], D / G [P] (numpy), total_pairs."""
+    dev = dt_img.device
+    dt_key = dt_img.to(torch.int64) * num_classes + dt_label.to(torch.int64)
+    gt_key = gt_img.to(torch.int64) * num_classes + gt_label.to(torch.int64)
+    keys = torch.unique(torch.cat([dt_key, gt_key]), sorted=True)
+    P = keys.numel()
+    dt_prob, gt_prob = torch.searchsorted(keys, dt_key), torch.searchsorted(keys, gt_key)
+    by_score = torch.sort(dt_score.to(torch.float64), descending=True, stable=True)[1]
+    dt_order = by_score[torch.sort(dt_prob[by_score], stable=True)[1]]
+    gt_order = torch.sort(gt_prob, stable=True)[1]
+    D = torch.bincount(dt_prob, minlength=P)[:P] if P else torch.zeros((0,), dtype=torch.int64, device=dev)
+    G = torch.bincount(gt_prob, minlength=P)[:P] if P else torch.zeros((0,), dtype=torch.int64, device=dev)
+    zero = torch.zeros((1,), dtype=torch.int64, device=dev)
+    if P and int(D.max()) > max_dets:
+        start = torch.cat([zero, torch.cumsum(D, 0)])[:-1]
+        rank = torch.arange(dt_order.numel(), device=dev) - start[dt_prob[dt_order]]
+        dt_order = dt_order[rank < max_dets]
+        D = D.clamp(max=max_dets)
+    dt_offset = torch.cat([zero, torch.cumsum(D, 0)])
+    gt_offset = torch.cat([zero, torch.cumsum(G, 0)])
+    iou_offset = torch.cat([zero, torch.cumsum(D * G, 0)])
+    keys_h, D_h, G_h = keys.cpu().numpy(), D.cpu().numpy(), G.cpu().numpy()
+    return {"dt_order": dt_order, "gt_order": gt_order, "dt_offset": dt_offset.to(torch.int32),
+            "gt_offset": gt_offset.to(torch.int32), "iou_offset": iou_offset, "image": keys_h // num_classes,
+            "category": keys_h % num_classes, "D": D_h, "G": G_h, "total_pairs": int((D_h * G_h).sum()),
+            "counts_host": (int(D_h.sum()), int(G_h.sum()), int(G_h.max()) if P else 0)}
+
+
+def _planes_of_target(target):
+    masks = target.get_field("masks")
+    if isinstance(masks, SegmentationMask):
+        masks = masks.convert("mask").instances.masks
+    if masks.dim() == 2:
+        masks = masks[None]
+    W, H = target.size
+    if tuple(masks.shape[-2:]) != (H, W):
+        raise ValueError("ground-truth masks of size %s for an image of %s" % (tuple(masks.shape[-2:]), (H, W)))
+    return (masks != 0) if masks.dtype not in (torch.uint8, torch.bool) else masks
+
+
+class COCOStyleEvaluator(object):
+    """evaluator = COCOStyleEvaluator(("bbox", "segm"), num_classes); evaluator.update(predictions, targets) per batch;
+    evaluator.summarize() -> {iou type: the 12 numbers AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl}.
+
+    Labels are the contiguous ones (1 .. num_classes - 1).  The largest number of ground truths of one (image, category)
+    pair the device matches is _C.EVAL_MAX_GT; larger problems are matched on the host."""
+
+    def __init__(self, iou_types=("bbox",), num_classes=81):
+        iou_types = tuple(iou_types)
+        for t in iou_types:
+            if t == "keypoints":
+                raise NotImplementedError("the keypoints IoU type (OKS) is not built")
+            if t not in ("bbox", "segm"):
+                raise ValueError("unknown IoU type %r" % (t,))
+        self.iou_types = iou_types
+        self.num_classes = int(num_classes)
+        self.iou_thrs, self.rec_thrs, self.area_rngs, self.max_dets = IOU_THRS, REC_THRS, AREA_RNGS, MAX_DETS
+        self.records = {t: [] for t in iou_types}
+        self.num_images = self.num_detections = self.num_groundtruths = 0
+        self.eval = {}
+
+    # ------------------------------------------------------------------ per batch
+    def update(self, predictions, targets):
+        """predictions, targets: two lists of BoxList (one per image), on the device or the CPU.  Predictions carry
+        `scores`, `labels` and, for segm, `mask`: dense bool planes [n, 1, H, W] of the image's size, or probabilities
+        [n, 1, M, M], which Masker(threshold=0.5, padding=1) pastes.  Targets carry `labels` and may carry `masks`
+        (either SegmentationMask mode), `iscrowd` and `area`."""
+        assert len(predictions) == len(targets), "one prediction per target"
+        segm = "segm" in self.iou_types
+        dev = targets[0].bbox.device if targets else torch.device("cpu")
+        preds, tgts = [], []
+        for pred, tgt in zip(predictions, targets):
+            tgt = tgt.convert("xyxy")
+            if tuple(pred.size) != tuple(tgt.size):
+                pred = pred.resize(tgt.size)
+            preds.append(pred.convert("xyxy").to(dev))
+            tgts.append(tgt)
+        n_dt, n_gt = [len(p) for p in preds], [len(t) for t in tgts]
+        i64 = dict(dtype=torch.int64, device=dev)
+        img = torch.arange(len(preds), **i64) + self.num_images
+        dt_img, gt_img = img.repeat_interleave(torch.tensor(n_dt, **i64)), img.repeat_interleave(torch.tensor(n_gt, **i64))
+        cat = lambda ts, **kw: torch.cat(ts) if ts else torch.zeros((0,), **kw)  # noqa: E731
+        dt_box = cat([p.bbox for p in preds]).reshape(-1, 4)
+        gt_box = cat([t.bbox for t in tgts]).reshape(-1, 4)
+        dt_label = cat([p.get_field("labels").to(**i64) for p in preds], **i64)
+        gt_label = cat([t.get_field("labels").to(**i64) for t in tgts], **i64)
+        dt_score = cat([p.get_field("scores").reshape(-1) for p in preds], device=dev)
+        gt_crowd = cat([(t.get_field("iscrowd").to(dev) != 0) if t.has_field("iscrowd") else torch.zeros((len(t),), dtype=torch.bool, device=dev)
+                        for t in tgts], dtype=torch.bool, device=dev)
+        for name, lab in (("prediction", dt_label), ("target", gt_label)):
+            if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= self.num_classes):
+                raise ValueError("%s labels must lie in [0, %d), got %d .. %d" % (name, self.num_classes, int(lab.min()), int(lab.max())))
+        self.num_images += len(preds)
+        self.num_detections += sum(n_dt)
+        self.num_groundtruths += sum(n_gt)
+        pr = build_problems(dt_img, dt_label, dt_score, gt_img, gt_label, self.num_classes)
+        do, go = pr["dt_order"], pr["gt_order"]
+        has_masks = [t.has_field("masks") for t in tgts]
+        gt_pack = dt_pack = None
+        if segm or any(m and not t.has_field("area") for t, m in zip(tgts, has_masks)):    # planes, or their pixel counts
+            gt_planes = [_planes_of_target(t) if m else torch.zeros((len(t), t.size[1], t.size[0]), dtype=torch.uint8, device=dev)
+                         for t, m in zip(tgts, has_masks)]
+            if segm and not all(m or len(t) == 0 for t, m in zip(tgts, has_masks)):
+                raise ValueError("segm evaluation needs ground-truth masks")
+            gt_pack = _C.mask_pack(gt_planes)
+        if segm:
+            dt_pack = _C.mask_pack(self._prediction_planes(preds))
+        # the ground truth's area: the field; else the mask's pixel count; else w * h of the xywh box
+        gt_wh = (gt_box[:, 2:] - gt_box[:, :2]) + 1
+        box_area = gt_wh[:, 0].to(torch.float64) * gt_wh[:, 1].to(torch.float64)
+        parts, k = [], 0
+        for t, m in zip(tgts, has_masks):
+            n = len(t)
+            if t.has_field("area"):
+                parts.append(t.get_field("area").to(device=dev, dtype=torch.float64).reshape(-1))
+            elif m:
+                parts.append(gt_pack[3][k:k + n].to(torch.float64))
+            else:
+                parts.append(box_area[k:k + n])
+            k += n
+        gt_area = cat(parts, dtype=torch.float64, device=dev)
+        offs = (pr["dt_offset"], pr["gt_offset"], pr["iou_offset"])
+        thrs, rngs = torch.from_numpy(self.iou_thrs), torch.from_numpy(self.area_rngs)
+        for iou_type in self.iou_types:
+            if iou_type == "bbox":
+                iou = _C.eval_iou(_C.EVAL_COCO_BBOX, *offs, pr["total_pairs"], dt_boxes=dt_box[do], gt_boxes=gt_box[go],
+                                  gt_crowd=gt_crowd[go])
+                dt_wh = (dt_box[:, 2:] - dt_box[:, :2]) + 1
+                dt_area = (dt_wh[:, 0].to(torch.float64) * dt_wh[:, 1].to(torch.float64))[do]
+            else:
+                dpk = (dt_pack[0], dt_pack[1][do], dt_pack[2][do], dt_pack[4][do])
+                gpk = (gt_pack[0], gt_pack[1][go], gt_pack[2][go], gt_pack[4][go])
+                counts = _C.mask_pair_counts(dpk, gpk, *offs, pr["total_pairs"])
+                iou = _C.eval_iou(_C.EVAL_COCO_SEGM, *offs, pr["total_pairs"], counts=counts, dt_area=dt_pack[3][do],
+                                  gt_area=gt_pack[3][go], gt_crowd=gt_crowd[go])
+                dt_area = dt_pack[3][do].to(torch.float64)
+            code = _C.EVAL_COCO_BBOX if iou_type == "bbox" else _C.EVAL_COCO_SEGM
+            dtm, dti, gti = _C.eval_match(code, iou, *offs, pr["counts_host"], gt_crowd[go], thrs, dt_area=dt_area,
+                                          gt_area=gt_area[go], area_rngs=rngs)
+            self._keep(iou_type, pr, dt_score[do].to(torch.float64).cpu().numpy(), dtm.cpu().numpy(), dti.cpu().numpy(),
+                       gti.cpu().numpy())
+
+    def _prediction_planes(self, preds):
+        """-> a list of [n_i, H_i, W_i] uint8 / bool tensors"""
+        from maskrcnn_benchmark.modeling.roi_heads.mask_head.inference import Masker
+
+        out, paste = [None] * len(preds), []
+        for i, p in enumerate(preds):
+            W, H = p.size
+            if len(p) == 0:
+                out[i] = torch.zeros((0, H, W), dtype=torch.uint8, device=p.bbox.device)
+                continue
+            masks = p.get_field("mask")
+            if masks.dim() != 4 or masks.shape[1] != 1:
+                raise ValueError("prediction masks must be [n, 1, H, W] planes or [n, 1, M, M] probabilities, got %s" % (tuple(masks.shape),))
+            if masks.dtype == torch.bool or masks.dtype == torch.uint8:
+                if tuple(masks.shape[-2:]) != (H, W):
+                    raise ValueError("dense prediction masks of size %s for an image of %s" % (tuple(masks.shape[-2:]), (H, W)))
+                out[i] = masks[:, 0].to(p.bbox.device)
+            else:
+                paste.append(i)
+        if paste:
+            pasted = Masker(threshold=0.5, padding=1)([preds[i].get_field("mask").to(preds[i].bbox.device) for i in paste],
+                                                      [preds[i] for i in paste])
+            for i, m in zip(paste, pasted):
+                out[i] = m[:, 0]
+        return out
+
+    def _keep(self, iou_type, pr, scores, dtm, dti, gti):
+        d, g = np.concatenate([[0], np.cumsum(pr["D"])]), np.concatenate([[0], np.cumsum(pr["G"])])
+        for p in range(len(pr["D"])):
+            self.records[iou_type].append({
+                "image": int(pr["image"][p]), "category": int(pr["category"][p]), "scores": scores[d[p]:d[p + 1]].copy(),
+                "dt_match": dtm[:, :, d[p]:d[p + 1]].copy(), "dt_ignore": dti[:, :, d[p]:d[p + 1]].copy(),
+                "gt_ignore": gti[:, g[p]:g[p + 1]].copy()})
+
+    # ------------------------------------------------------------------ once per evaluation
+    def accumulate(self):
+        """-> {iou type: {"precision": [T, R, K, A, M], "recall": [T, K, A, M]}}, K = num_classes - 1 (category k + 1), cells
+        never filled are -1"""
+        for iou_type in self.iou_types:
+            self.eval[iou_type] = accumulate(self.records[iou_type], self.num_classes, self.iou_thrs, self.rec_thrs,
+                                             len(self.area_rngs), self.max_dets)
+        return self.eval
+
+    def summarize(self):
+        self.accumulate()
+        self.stats = OrderedDict((t, summarize(self.eval[t], self.iou_thrs, self.max_dets)) for t in self.iou_types)
+        return self.stats
+
+
+def accumulate(records, num_classes, iou_thrs=IOU_THRS, rec_thrs=REC_THRS, num_areas=len(AREA_RNGS), max_dets=MAX_DETS):
+    T, R, K, A, M = len(iou_thrs), len(rec_thrs), num_classes - 1, num_areas, len(max_dets)
+    precision = -np.ones((T, R, K, A, M))
+    recall = -np.ones((T, K, A, M))
+    by_cat = {}
+    for r in sorted(records, key=lambda r: r["image"]):       # a stable sort: images in the order they arrived
+        by_cat.setdefault(r["category"], []).append(r)
+    for k in range(K):
+        E = by_cat.get(k + 1, [])
+        if not E:
+            continue
+        for a in range(A):
+            gt_ig = np.concatenate([e["gt_ignore"][a] for e in E])
+            npig = np.count_nonzero(gt_ig == 0)
+            if npig == 0:
+                continue
+            for m, max_det in enumerate(max_dets):
+                scores = np.concatenate([e["scores"][:max_det] for e in E])
+                inds = np.argsort(-scores, kind="mergesort")
+                dtm = np.concatenate([e["dt_match"][a][:, :max_det] for e in E], axis=1)[:, inds]
+                dt_ig = np.concatenate([e["dt_ignore"][a][:, :max_det] for e in E], axis=1)[:, inds]
+                tps = np.logical_and(dtm >= 0, np.logical_not(dt_ig))
+                fps = np.logical_and(dtm < 0, np.logical_not(dt_ig))
+                tp_sum = np.cumsum(tps, axis=1).astype(dtype=np.float64)
+                fp_sum = np.cumsum(fps, axis=1).astype(dtype=np.float64)
+                for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+                    nd = len(tp)
+                    rc = tp / npig
+                    pr = tp / (fp + tp + np.spacing(1))
+                    recall[t, k, a, m] = rc[-1] if nd else 0
+                    pr = np.maximum.accumulate(pr[::-1])[::-1]          # non-increasing from the right
+                    q = np.zeros((R,))
+                    idx = np.searchsorted(rc, rec_thrs, side="left")
+                    ok = idx < nd
+                    q[ok] = pr[idx[ok]]
+                    precision[t, :, k, a, m] = q
+    return {"precision": precision, "recall": recall}
+
+
+def summarize(ev, iou_thrs=IOU_THRS, max_dets=MAX_DETS):
+    """-> the 12 numbers (STAT_NAMES): the mean of the cells greater than -1, or -1 when there are none"""
+    def stat(ap, thr=None, area=0, m=len(max_dets) - 1):
+        s = ev["precision"] if ap else ev["recall"]
+        if thr is not None:
+            s = s[np.nonzero(np.isclose(iou_thrs, thr))[0]]
+        s = s[:, :, :, area, m] if ap else s[:, :, area, m]
+        s = s[s > -1]
+        return float(np.mean(s)) if s.size else -1.0
+
+    return np.array([stat(1), stat(1, 0.5), stat(1, 0.75), stat(1, area=1), stat(1, area=2), stat(1, area=3),
+                     stat(0, m=0), stat(0, m=1), stat(0, m=2), stat(0, area=1), stat(0, area=2), stat(0, area=3)])

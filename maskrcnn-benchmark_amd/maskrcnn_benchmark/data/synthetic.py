@@ -45,6 +45,9 @@ class SyntheticCOCODataset(torch.utils.data.Dataset):
     def get_img_info(self, index):
         return {"height": self.height, "width": self.width}
 
+    def get_groundtruth(self, index):
+        return self[index][1]
+
     def __getitem__(self, index):
         g = torch.Generator().manual_seed(self.seed * 1000003 + index)
         H, W = self.height, self.width

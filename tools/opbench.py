@@ -584,6 +584,90 @@ def bench_polygons(C, iters):
     return out
 
 
+def bench_evaluation(C, iters):
+    """detection evaluation (csrc/evaluate.hip): the 100 pasted detections of bench_masker against the 20 instances of
+    bench_polygons, one 800 x 1333 image, all in one category (every pair is a problem pair: one problem of 100 x 20).
+    mask_pack: bytes = the uint8 planes read + the bit rows written (frac_of_copy_peak counts the bytes READ only);
+    mask_pair_counts: bytes = the words of both planes inside every pair's intersected extents; eval_iou + eval_match: the
+    IoU matrix and the 40 lanes' records.  Last row: the same intersections from torch operators on the same device planes
+    (planes to float, one matmul: exact, the counts stay below 2^24), written in the same run."""
+    from maskrcnn_benchmark.structures.segmentation_mask import PolygonList
+    g = torch.Generator().manual_seed(5)                      # bench_masker's detections
+    N, H, W, M = 100, 800, 1333, 28
+    s_ = torch.exp(torch.empty(N, 2).uniform_(np.log(32), np.log(800), generator=g))
+    xy = torch.rand(N, 2, generator=g) * torch.tensor([W - 32.0, H - 32.0])
+    boxes = torch.cat([xy, xy + s_], 1).cuda()
+    maps = torch.sigmoid(3 * torch.randn(N, 1, M, M, generator=g)).cuda()
+    _, views = C.paste_masks(maps, boxes, [(H, W)], 0.5, 1, counts=[N])
+    dt = views[0][:, 0]
+    rng = np.random.RandomState(11)                           # bench_polygons' instances
+    G = 20
+    insts = []
+    for k in range(G):
+        hw_, hh_ = np.exp(rng.uniform(np.log(12), np.log(330), 2))
+        cx, cy = rng.uniform(hw_, W - hw_), rng.uniform(min(hh_, H / 2 - 1), max(H - hh_, H / 2 + 1))
+        polys = []
+        for fx, fy in ([(1.0, 1.0)] if k % 4 != 3 else [(1.0, 0.6), (0.6, 1.0)]):
+            n = int(rng.randint(24, 201))
+            a = np.arange(n) * (2 * np.pi / n)
+            r = 1 + 0.08 * rng.uniform(-1, 1, n)
+            polys.append(np.stack([cx + fx * hw_ * r * np.cos(a), cy + fy * hh_ * r * np.sin(a)], 1).reshape(-1).tolist())
+        insts.append(polys)
+    pk = PolygonList(insts, (W, H)).packed().to("cuda")
+    gt = C.polygons_to_masks(pk.verts, pk.poly_offset, pk.inst_offset, H, W)
+    WW = (W + 63) // 64
+    out = []
+    us = dev_time_us(lambda: C.mask_pack(dt), iters)
+    out.append(_entry("mask_pack N=100 800x1333 (pasted detections)", us, N * H * W + N * H * WW * 8,
+                      {"frac_of_copy_peak_bytes_read": round(N * H * W / us / 1e3 / 6290.0, 4)}))
+    # the entry point alone, sizes and offsets already on the device (the rows above and below include the wrapper's host work)
+    from maskrcnn_benchmark import _lib
+    words, word_offset, hw, area, extent = C.mask_pack(dt)
+    plane_offset = (torch.arange(N, dtype=torch.int64) * (H * W)).cuda()
+    dt8 = dt.view(torch.uint8)
+    raw = lambda: _lib.check(_lib.lib.detops_mask_pack(  # noqa: E731
+        dt8.data_ptr(), plane_offset.data_ptr(), hw.data_ptr(), N, H * WW, word_offset.data_ptr(), words.data_ptr(),
+        area.data_ptr(), extent.data_ptr(), _lib.stream_of(words)), "mask_pack")
+    us = dev_time_us(raw, iters)
+    out.append(_entry("detops_mask_pack entry point, N=100 800x1333, prebuilt offsets", us, N * H * W + N * H * WW * 8,
+                      {"frac_of_copy_peak_bytes_read": round(N * H * W / us / 1e3 / 6290.0, 4)}))
+    us = dev_time_us(lambda: C.mask_pack(gt), iters)
+    out.append(_entry("mask_pack N=20 800x1333 (ground-truth planes)", us, G * H * W + G * H * WW * 8,
+                      {"frac_of_copy_peak_bytes_read": round(G * H * W / us / 1e3 / 6290.0, 4)}))
+    dp, gp = C.mask_pack(dt), C.mask_pack(gt)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32).cuda()  # noqa: E731
+    offs = (i32([0, N]), i32([0, G]), torch.tensor([0, N * G], dtype=torch.int64).cuda())
+    pick = lambda p: (p[0], p[1], p[2], p[4])  # noqa: E731
+    ed, eg = dp[4].cpu().numpy().astype(np.int64), gp[4].cpu().numpy().astype(np.int64)
+    rows = np.maximum(np.minimum(ed[:, None, 1], eg[None, :, 1]) - np.maximum(ed[:, None, 0], eg[None, :, 0]) + 1, 0)
+    cols = np.maximum(np.minimum(ed[:, None, 3], eg[None, :, 3]) - np.maximum(ed[:, None, 2], eg[None, :, 2]) + 1, 0)
+    pair_bytes = int((rows * cols).sum()) * 16
+    us = dev_time_us(lambda: C.mask_pair_counts(pick(dp), pick(gp), *offs, N * G), iters)
+    out.append(_entry("mask_pair_counts 100 x 20 pairs 800x1333", us, pair_bytes,
+                      {"overlapping_pairs": int(((rows * cols) > 0).sum()), "words_per_pair_mean": int((rows * cols).mean())}))
+    counts = C.mask_pair_counts(pick(dp), pick(gp), *offs, N * G)
+    crowd = torch.zeros((G,), dtype=torch.uint8).cuda()
+    thrs = torch.from_numpy(np.linspace(0.5, 0.95, 10))
+    rngs = torch.tensor([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], dtype=torch.float64)
+    da, ga = dp[3].double(), gp[3].double()
+
+    def iou_match():
+        iou = C.eval_iou(C.EVAL_COCO_SEGM, *offs, N * G, counts=counts, dt_area=dp[3], gt_area=gp[3], gt_crowd=crowd)
+        return C.eval_match(C.EVAL_COCO_SEGM, iou, *offs, (N, G, G), crowd, thrs, dt_area=da, gt_area=ga, area_rngs=rngs)
+
+    us = dev_time_us(iou_match, iters)
+    out.append(_entry("eval_iou + eval_match 100 x 20, 4 x 10 lanes", us, N * G * 12 + 40 * N * 5 + 4 * G))
+    gt8 = gt
+
+    def torch_counts():
+        return dt8.reshape(N, -1).float() @ gt8.reshape(G, -1).float().t()
+
+    us = dev_time_us(torch_counts, max(5, iters // 5), warmup=2)
+    same = bool(torch.equal(torch_counts().to(torch.int32).reshape(-1), counts))
+    out.append(_entry("torch: planes.float() matmul, same 100 x 20 intersections", us, (N + G) * H * W * 5, {"equal_counts": same}))
+    return out
+
+
 def copy_ceiling(iters):
     a = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
     b = torch.empty_like(a)
@@ -647,6 +731,8 @@ def main():
         res += bench_masker(C, args.iters)
     if not only or "polygons" in only:
         res += bench_polygons(C, args.iters)
+    if not only or "evaluation" in only:
+        res += bench_evaluation(C, args.iters)
     if not only or "frozen_bn" in only:
         res += bench_frozen_bn(C, args.iters)
     if not only or "focal" in only:
