@@ -23,6 +23,10 @@ const Key kKeys[] = {
     {"roi_bwd_extras", &DetopsTuning::roi_bwd_extras},   {"nms_no_repair", &DetopsTuning::nms_no_repair},
     {"nms_no_presorted", &DetopsTuning::nms_no_presorted}, {"nms_debug", &DetopsTuning::nms_debug},
 };
+// one key per field: a field without a key or a key without a field stops the build (the Python key list is held to
+// both by tests/test_abi.py)
+static_assert(sizeof(DetopsTuning) == sizeof(int) * (sizeof(kKeys) / sizeof(kKeys[0])),
+              "struct DetopsTuning and kKeys[] must list the same switches");
 
 bool set_key(DetopsTuning& t, const char* key, size_t len, int value) {
   for (const Key& k : kKeys)

@@ -7,7 +7,6 @@ with implementations that run the oracle (oracle/detops_oracle.c) on numpy copie
 tests/ imports this module.
 """
 import contextlib
-import os
 
 import numpy as np
 import torch
@@ -274,17 +273,10 @@ def _emu_lib_patches():
     """The PRODUCT's own `_C` wrappers (argument checks, marshalling, workspaces, autograd functions) on CPU tensors: the
     library handle they call is the host-emulation build of the same HIP sources (same C ABI, host pointers), the
     CUDA-only guards are lifted and `on_device` says yes.  Nothing of `_C`'s operator surface is replaced."""
-    import ctypes
-
     import emu
-    from maskrcnn_benchmark import _lib
-    emu.lib()                                   # builds tests/emu/libdetops_emu.so when needed
-    lib = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(emu.__file__)), "libdetops_emu.so"))
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:                      # the two *_cpu_* entry points and detops_version exist in the device build only
-            fn.restype, fn.argtypes = res, args
-    return {"lib": lib, "_need_cuda": lambda name, *tensors: None, "stream_of": lambda t: None,
+
+    # emu.lib(): built when needed, bound from the table the device build is bound from (maskrcnn_benchmark/_abi.py)
+    return {"lib": emu.lib(), "_need_cuda": lambda name, *tensors: None, "stream_of": lambda t: None,
             "_on_device": lambda t: _C._NOSPAN, "on_device": lambda t: True}
 
 

@@ -8,85 +8,13 @@ import subprocess
 
 import numpy as np
 
+from maskrcnn_benchmark import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-c_int, c_float, _P = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-SIGNATURES = {
-    "detops_tuning_set": (c_int, [ctypes.c_char_p, c_int]),
-    "detops_tuning_get": (c_int, [ctypes.c_char_p, _P]),
-    "detops_roi_align_forward_f32": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int, _P]),
-    "detops_roi_align_backward_f32": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int, c_int, _P]),
-    "detops_roi_align_fpn_forward_f32": (
-        c_int, [_P, _P, _P, _P, c_int, _P, _P, _P] + [c_int] * 8 + [c_float, c_float, c_float, _P]),
-    "detops_roi_align_fpn_backward_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P] + [c_int] * 8 + [_P]),
-    "detops_roi_align_fpn_backward_ws_f32": (
-        c_int, [_P, _P, _P, _P, _P, _P, _P] + [c_int] * 8 + [_P, ctypes.c_size_t, _P]),
-    "detops_roi_align_fpn_backward_prepare_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_P, ctypes.c_size_t, _P]),
-    "detops_roi_align_fpn_backward_prepared_f32": (c_int, [_P] * 5 + [c_int] * 7 + [_P, ctypes.c_size_t, _P]),
-    "detops_roi_align_backward_ws_f32": (
-        c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int, c_int, _P, ctypes.c_size_t, _P]),
-    "detops_roi_align_backward_workspace_bytes": (ctypes.c_size_t, [_P, _P] + [c_int] * 6),
-    "detops_roi_align_forward_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
-    "detops_roi_align_forward_ws_f32": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int, _P, ctypes.c_size_t, _P]),
-    "detops_roi_align_fpn_forward_ws_f32": (
-        c_int, [_P, _P, _P, _P, c_int, _P, _P, _P] + [c_int] * 8 + [c_float, c_float, c_float, _P, ctypes.c_size_t, _P]),
-    "detops_match_boxes_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
-    "detops_match_boxes_f32": (c_int, [_P, _P, _P] + [c_int] * 4 + [c_float, c_float, c_int, _P, _P, ctypes.c_size_t, _P]),
-    "detops_sample_labels_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
-    "detops_sample_labels": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint64, _P, _P, _P, _P, _P,
-                                     ctypes.c_size_t, _P]),
-    "detops_sample_labels_dseed": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint64, _P, _P, _P, _P, _P, _P,
-                                     ctypes.c_size_t, _P]),
-    "detops_mask_targets": (c_int, [_P, c_int, _P, _P] + [c_int] * 5 + [_P, _P]),
-    "detops_match_labels": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "detops_roi_head_targets_f32": (c_int, [_P] * 8 + [c_int] * 4 + [c_float] * 4 + [_P] * 6),
-    "detops_fastrcnn_loss_workspace_bytes": (ctypes.c_size_t, [c_int]),
-    "detops_fastrcnn_loss_f32": (c_int, [_P] * 4 + [c_int] * 4 + [c_float] + [_P] * 4 + [ctypes.c_size_t, _P]),
-    "detops_mask_loss_workspace_bytes": (ctypes.c_size_t, [c_int]),
-    "detops_mask_loss_f32": (c_int, [_P] * 3 + [c_int] * 3 + [_P] * 3 + [ctypes.c_size_t, _P]),
-    "detops_head_loss_backward_f32": (c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P]),
-    "detops_rpn_decode_f32": (c_int, [_P] * 5 + [c_int] * 5 + [c_float] * 6 + [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P]),
-    "detops_rpn_loss_workspace_bytes": (ctypes.c_size_t, []),
-    "detops_rpn_loss_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float,
-                                    _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "detops_rpn_loss_backward_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "detops_roi_pool_forward_f32": (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [c_float, _P]),
-    "detops_roi_pool_backward_f32": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_P]),
-    "detops_nms_workspace_bytes": (ctypes.c_size_t, [c_int]),
-    "detops_nms_f32": (c_int, [_P, _P, c_int, c_float, _P, _P, _P, ctypes.c_size_t, _P]),
-    "detops_nms_batched_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
-    "detops_nms_batched_f32": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, ctypes.c_size_t, _P]),
-    "detops_nms_batched_mask_f32": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, ctypes.c_size_t, _P]),
-    "detops_sigmoid_focal_loss_forward_f32": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, _P]),
-    "detops_sigmoid_focal_loss_backward_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P]),
-    "detops_sigmoid_focal_loss_backward_scalar_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P]),
-    "detops_sigmoid_focal_loss_forward_sum_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P]),
-    "detops_sigmoid_focal_loss_sum_workspace_bytes": (ctypes.c_size_t, []),
-    "detops_sigmoid_focal_loss_forward_sum_ws_f32": (
-        c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, ctypes.c_size_t, _P]),
-    "detops_sigmoid_focal_loss_forward_partial_sums_f32": (
-        c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P]),
-    "detops_frozen_bn_act_forward": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
-    "detops_frozen_bn_act_backward": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
-    "detops_deform_psroi_pool_forward_f32": (c_int, [_P] * 5 + [c_int] * 7 + [c_float] + [c_int] * 5 + [c_float, _P]),
-    "detops_deform_psroi_pool_backward_f32": (
-        c_int, [_P] * 7 + [c_int] * 7 + [c_float] + [c_int] * 5 + [c_float, c_int, _P]),
-    "detops_deformable_im2col": (c_int, [_P, _P, _P, _P] + [c_int] * 14 + [_P]),
-    "detops_deformable_col2im": (c_int, [_P, _P, _P, _P] + [c_int] * 14 + [_P]),
-    "detops_deformable_col2im_workspace_bytes": (ctypes.c_size_t, [c_int] * 13),
-    "detops_deformable_col2im_ws": (c_int, [_P, _P, _P, _P] + [c_int] * 14 + [_P, ctypes.c_size_t, _P]),
-    "detops_deform_conv_forward_fused_workspace_bytes": (ctypes.c_size_t, [c_int] * 15),
-    "detops_deform_conv_forward_fused": (c_int, [_P] * 6 + [c_int] * 15 + [_P, ctypes.c_size_t, _P]),
-    "detops_nchw_to_nhwc": (c_int, [_P, _P] + [c_int] * 4 + [_P]),
-    "detops_deformable_nhwc_supported": (c_int, [c_int] * 4),
-    "detops_deformable_im2col_nhwc": (c_int, [_P, _P, _P, _P] + [c_int] * 14 + [_P]),
-    "detops_deformable_coord_nhwc": (c_int, [_P] * 6 + [c_int] * 14 + [_P]),
-    "detops_deformable_transposed_sample_workspace_bytes": (ctypes.c_size_t, [c_int] * 13),
-    "detops_deformable_transposed_sample": (c_int, [_P, _P, _P, _P] + [c_int] * 15 + [_P, ctypes.c_size_t, _P]),
-    "detops_deformable_col2im_nhwc": (c_int, [_P, _P, _P, _P] + [c_int] * 14 + [_P, ctypes.c_size_t, _P]),
-    "detops_deformable_col2im_coord": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 14 + [_P]),
-}
+c_int, _P = ctypes.c_int, ctypes.c_void_p
+TUNING_KEYS = _abi.TUNING_KEYS
 
 
 def lib():
@@ -94,14 +22,8 @@ def lib():
     if _LIB is None:
         subprocess.check_call(["make", "-s", "-C", _HERE])
         _LIB = ctypes.CDLL(os.path.join(_HERE, "libdetops_emu.so"))
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(_LIB, name)
-            fn.restype, fn.argtypes = res, args
+        _abi.bind(_LIB, require_all=False)   # the emulation leaves some sources out (Makefile: SRCS)
     return _LIB
-
-
-TUNING_KEYS = ("roi_bwd_impl", "roi_bwd_seg", "nms_fault", "nms_spin_budget", "roi_bwd_ring", "roi_bwd_ct", "roi_bwd_split", "roi_bwd_maxseg", "roi_bwd_extras", "roi_bwd_groups", "roi_bwd_scan_ct", "roi_bwd_debug", "roi_fwd_impl", "roi_fwd_records", "roi_fwd_ct",
-               "roi_fwd_order", "roi_fwd_order_mink", "dcn_col2im", "dcn_fused", "dcn_gather_xcd", "dcn_nhwc", "dcn_ell_build", "nms_fused", "nms_no_repair", "nms_no_presorted", "nms_debug")
 
 
 def tuning_set(key, value):
@@ -356,7 +278,7 @@ def rpn_decode(box_regression, topk_idx, topk_scores, anchors, image_hw, weights
 
 
 # ---------------------------------------------------------------------------------- deformable conv
-_DT = {np.dtype(np.float32): 0, np.dtype(np.float16): 1}
+_DT = {np.dtype(np.float32): _abi.F32, np.dtype(np.float16): _abi.F16}
 
 
 def deform_conv_forward_fused(im, weight, offset, mask, bias, pad, stride, dil, dg):
@@ -530,12 +452,9 @@ def nms_batched(boxes, scores, offsets, max_n, thr, mask=False, status=None):
     if status is not None:
         km = np.full((boxes.shape[0],), 7, np.uint8) if mask else None
         keep = None if mask else np.full((boxes.shape[0],), -1, np.int64)
-        fn = lib().detops_nms_batched_status_f32
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 5 + \
-                      [ctypes.c_size_t, ctypes.c_void_p]
-        rc = fn(_p(boxes), _p(scores), _p(offsets), S, max_n, thr, None if mask else _p(keep), _p(km) if mask else None,
-                _p(num), _p(status), _p(ws), nbytes, None)
+        rc = lib().detops_nms_batched_status_f32(_p(boxes), _p(scores), _p(offsets), S, max_n, thr,
+                                                 None if mask else _p(keep), _p(km) if mask else None, _p(num), _p(status),
+                                                 _p(ws), nbytes, None)
         assert rc == 0, rc
         return (km if mask else keep), num
     if mask:
@@ -741,10 +660,7 @@ def pack(dst, arrays, offsets):
 
 
 def sgd_momentum_flat(p, g, m, split, lr_w, wd_w, lr_b, wd_b, momentum):
-    fn = lib().detops_sgd_momentum_flat_f32
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_float] * 5 + [ctypes.c_void_p]
-    return fn(_p(p), _p(g), _p(m), p.size, int(split), lr_w, wd_w, lr_b, wd_b, momentum, None)
+    return lib().detops_sgd_momentum_flat_f32(_p(p), _p(g), _p(m), p.size, int(split), lr_w, wd_w, lr_b, wd_b, momentum, None)
 
 
 # ---------------------------------------------------------------------------------- FPN top-down step (fpn_topdown.hip)

@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary (`-m "not gpu"`): the C-ABI library builds for gfx950,
-loads, exports every symbol include/detops.h declares, and the Python mirror of the reference
-operator API has the reference's names and fails loudly without a GPU path."""
+loads, exports every symbol include/detops.h declares, the one ctypes table both builds are bound
+from (maskrcnn_benchmark/_abi.py) agrees with the header type for type, and the Python mirror of the
+reference operator API has the reference's names and fails loudly without a GPU path."""
 import ctypes
 import os
 import re
@@ -19,6 +20,45 @@ def declared_symbols():
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(detops_[a-z0-9_]+)\s*\(", src)))
+
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64, "detops_stream_t": ctypes.c_void_p}
+_POINTEES = set(_SCALARS) - {"detops_stream_t"} | {"void", "char", "unsigned char", "signed char", "double", "int32_t", "uint8_t", "uint32_t"}
+
+
+def _ctype(decl):
+    """One C parameter or return type (the parameter name, if any, still attached) -> its ctype; raises on a base type
+    this rule does not know."""
+    decl = decl.strip()
+    stars = decl.count("*") + decl.count("[")
+    words = [w for w in re.sub(r"\[[^\]]*\]|\*", " ", decl).split() if w != "const"]
+    for n in (2, 1):                            # "unsigned char" before "unsigned"
+        base = " ".join(words[:n])
+        if base in (_POINTEES if stars else _SCALARS) and len(words) - n <= 1:   # at most the parameter's name is left
+            break
+    else:
+        raise ValueError("unknown type in %r" % decl)
+    if not stars:
+        return _SCALARS[base]
+    return ctypes.c_char_p if (base, stars) == ("char", 1) else ctypes.c_void_p
+
+
+def header_prototypes():
+    """{name: (restype, [argtypes])} of every prototype of include/detops.h"""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    out = {}
+    for ret, name, args in re.findall(r"([\w \t\*]+?)\b(detops_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, name
+        args = [] if args.strip() == "void" else args.split(",")
+        out[name] = (_ctype(ret), [_ctype(a) for a in args])
+    return out
+
+
+def header_defines():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return {k: int(v) for k, v in re.findall(r"^#define\s+(DETOPS_\w+)\s+\(?(-?\d+)\)?\s*$", src, flags=re.M)}
 
 
 @pytest.fixture(scope="module")
@@ -60,6 +100,79 @@ def test_python_binding_covers_header_and_reference_names(lib):
                  "modulated_deform_conv_forward", "modulated_deform_conv_backward",
                  "deform_psroi_pooling_forward", "deform_psroi_pooling_backward"):
         assert callable(getattr(_C, name)), name
+
+
+def test_binding_table_agrees_with_the_header():
+    """every return type and every argument of include/detops.h against maskrcnn_benchmark/_abi.py (ctypes trusts the
+    table: a wrong width is a garbage size or pointer in a kernel, not a Python error), and the codes the header defines"""
+    from maskrcnn_benchmark import _abi
+
+    protos = header_prototypes()
+    assert sorted(protos) == declared_symbols()          # no prototype skipped by the parser
+    assert sorted(_abi.SIGNATURES) == sorted(protos)
+    wrong = {n: (protos[n], tuple(_abi.SIGNATURES[n])) for n in protos
+             if (protos[n][0], protos[n][1]) != (_abi.SIGNATURES[n][0], list(_abi.SIGNATURES[n][1]))}
+    assert not wrong, wrong
+    d = header_defines()
+    assert {k: v for k, v in d.items() if k.startswith("DETOPS_E") and not k.startswith("DETOPS_EVAL_")} \
+        == {msg.split()[0]: code for code, msg in _abi.ERRORS.items()}
+    assert d["DETOPS_ABI_VERSION"] == _abi.ABI_VERSION
+    assert (d["DETOPS_F32"], d["DETOPS_F16"], d["DETOPS_BF16"]) == (_abi.F32, _abi.F16, _abi.BF16)
+
+
+def test_type_rule_rejects_what_it_does_not_know():
+    assert _ctype("const char* key") is ctypes.c_char_p
+    assert _ctype("const char** arch") is ctypes.c_void_p
+    assert _ctype("const unsigned char* valid") is ctypes.c_void_p
+    assert _ctype("const float* const* inputs_host") is ctypes.c_void_p
+    assert _ctype("int64_t n") is ctypes.c_int64
+    for bad in ("long n", "unsigned n", "double x", "char c", "struct foo* p", "int"  " a b"):
+        with pytest.raises(ValueError):
+            _ctype(bad)
+
+
+def test_tuning_keys_agree_in_struct_key_table_and_python():
+    """a key missing from the Python list would leak a switch from one test into the next (tests/conftest.py resets the
+    keys of this list); the struct and kKeys[] are also tied by a static_assert in tuning.hip"""
+    from maskrcnn_benchmark import _abi
+
+    strip = lambda p: re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(CSRC, p)).read(), flags=re.S)  # noqa: E731
+    body = re.search(r"struct DetopsTuning\s*\{(.*?)\};", strip("detops_common.h"), flags=re.S).group(1)
+    decls = [d.strip() for d in body.split(";") if d.strip()]
+    fields = [re.fullmatch(r"int\s+(\w+)", d).group(1) for d in decls]       # a non-int field fails here
+    table = re.search(r"kKeys\[\]\s*=\s*\{(.*?)\};", strip("tuning.hip"), flags=re.S).group(1)
+    keys = re.findall(r'\{\s*"(\w+)"\s*,\s*&DetopsTuning::(\w+)\s*\}', table)
+    assert len(keys) == table.count("{") and all(k == f for k, f in keys)
+    assert len(set(_abi.TUNING_KEYS)) == len(_abi.TUNING_KEYS)
+    assert len(set(fields)) == len(fields) and len(keys) == len(set(keys))
+    assert set(fields) == set(_abi.TUNING_KEYS)
+    assert {k for k, _ in keys} == set(_abi.TUNING_KEYS)
+
+
+def test_emulation_library_is_bound_from_the_same_table():
+    """tests/emu binds its host build of the HIP sources from the table: everything it calls is typed, everything the
+    library exports is bound, and what it does not export is exactly what tests/emu/Makefile leaves out"""
+    import emu
+    from maskrcnn_benchmark import _abi
+
+    handle = emu.lib()
+    bound = {n for n in _abi.SIGNATURES if getattr(getattr(handle, n, None), "argtypes", None) is not None}
+    exported = {n for n in _abi.SIGNATURES if hasattr(handle, n)}
+    assert bound == exported == _abi.bind(handle, require_all=False)
+    emu_dir = os.path.dirname(os.path.abspath(emu.__file__))
+    used = set(re.findall(r"\bdetops_[a-z0-9_]+", open(os.path.join(emu_dir, "__init__.py")).read()))
+    used.discard("detops_emu_stats")             # the emulation's own counter dump, not part of the ABI
+    assert used <= bound, sorted(used - bound)
+    srcs = re.search(r"^SRCS\s*:?=(.*)$", open(os.path.join(emu_dir, "Makefile")).read(), flags=re.M).group(1).split()
+    defined_in = {}
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(".hip"):
+            for n in re.findall(r"^DETOPS_API\s[^(;]*?\b(detops_[a-z0-9_]+)\s*\(", open(os.path.join(CSRC, f)).read(), flags=re.M):
+                assert defined_in.setdefault(n, f) == f, n
+    assert set(srcs) <= set(defined_in.values()), srcs
+    assert sorted(defined_in) == sorted(_abi.SIGNATURES)
+    left_out = {n for n, f in defined_in.items() if f not in srcs}
+    assert left_out and set(_abi.SIGNATURES) - exported == left_out
 
 
 def test_layers_api_names_match_reference():
