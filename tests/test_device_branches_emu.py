@@ -1,7 +1,8 @@
 """The branches the model only takes on the GPU (`_C.on_device`): fused label / sampled-slot / proposal-decode launches
-and the batched hand-over of the proposals from the RPN to the box head — driven WITHOUT a GPU by serving the kernels of
-csrc/targets.hip from the host emulation (cpu_shim backend "emu-device") and compared with the ATen compositions the
-CPU path runs (which tests/test_model_cpu.py pins to the reference-generated fixtures)."""
+and the batched hand-over of the proposals from the RPN to the box head — driven WITHOUT a GPU through the product's own
+`_C` wrappers over the host-emulation build of the HIP sources (cpu_shim backend "emu-lib") and compared with the ATen
+compositions the same wrappers serve with `device_branches=False` (the CPU path, which tests/test_model_cpu.py pins to the
+reference-generated fixtures)."""
 import numpy as np
 import pytest
 import torch
@@ -71,10 +72,10 @@ def test_rpn_proposals_device_branch_equals_the_composite(min_size):
     anchors, obj, reg = _rpn_inputs(rng, sizes)
     targets = _targets(rng, sizes, [2, 6])
     post = RPNPostProcessor(300, 300, 0.7, min_size, BoxCoder((1.0, 1.0, 1.0, 1.0)), fpn_post_nms_top_n=400).train()
-    with cpu_shim.install("emu"):
+    with cpu_shim.install("emu-lib", device_branches=False):
         ref = post(anchors, obj, reg, targets)
     begin_step()
-    with cpu_shim.install("emu-device"):
+    with cpu_shim.install("emu-lib"):
         out = post(anchors, obj, reg, targets)
         boxes, valid = stack_proposals(out)
         assert boxes is out[0].batch_rows[0]["boxes"]                         # handed over as the batch, no copy
@@ -113,10 +114,10 @@ def test_box_head_subsample_device_branch_equals_the_composite(monkeypatch):
         _, _, idx, val = emu.sample_labels(labels.numpy(), 64, 16, seed=9)
         return torch.from_numpy(idx), torch.from_numpy(val)
     monkeypatch.setattr(ev.fg_bg_sampler, "sample_fixed", sample_fixed)
-    with cpu_shim.install("emu"):
+    with cpu_shim.install("emu-lib", device_branches=False):
         ref = ev.subsample(props, targets)
     begin_step()
-    with cpu_shim.install("emu-device"):
+    with cpu_shim.install("emu-lib"):
         out = ev.subsample(props, targets)
     assert len(out) == len(ref) == 2
     for o, r in zip(out, ref):
@@ -135,10 +136,10 @@ def test_rpn_labels_device_branch_equals_the_composite():
     anchors, _, _ = _rpn_inputs(rng, sizes)
     targets = _targets(rng, sizes, [4, 1])
     ev = make_rpn_loss_evaluator(_cfg(), BoxCoder((1.0, 1.0, 1.0, 1.0)))
-    with cpu_shim.install("emu"):
+    with cpu_shim.install("emu-lib", device_branches=False):
         ref = ev._match(anchors, targets)
     begin_step()
-    with cpu_shim.install("emu-device"):
+    with cpu_shim.install("emu-lib"):
         out = ev._match(anchors, targets)
     assert out[0].dtype == ref[0].dtype == torch.float32
     for a, b in zip(out, ref):
@@ -161,7 +162,7 @@ def test_tiny_mask_rcnn_trains_through_the_device_branches(monkeypatch):
     model = build_detection_model(cfg).train()
     calls = {}
     # (the counting wrappers are undone INSIDE the install block: undone after it they would re-install the shims they wrap)
-    with cpu_shim.install("emu-device"), monkeypatch.context() as mp:
+    with cpu_shim.install("emu-lib"), monkeypatch.context() as mp:
         for name in ("match_boxes", "sample_labels", "match_labels", "roi_head_targets", "rpn_decode", "mask_targets"):
             fn = getattr(_C, name)
 
@@ -179,12 +180,11 @@ def test_tiny_mask_rcnn_trains_through_the_device_branches(monkeypatch):
     assert sum(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in model.parameters()) > 10
 
 
-@pytest.mark.parametrize("backend", ["emu-device", "emu-lib"])
-def test_tiny_mask_rcnn_with_the_fused_head_losses_equals_the_aten_losses(backend, monkeypatch):
+def test_tiny_mask_rcnn_with_the_fused_head_losses_equals_the_aten_losses(monkeypatch):
     """DETOPS_HEAD_LOSS=fused (the default; "torch" keeps the ATen compositions): the value + gradient kernels of csrc/head_loss.hip in the detector — same losses
     and same parameter gradients as the ATen compositions (same weights, same batch, same sampler draws).
-    "emu-lib": through the product's own `_C.fastrcnn_loss` / `_C.mask_loss` autograd functions (and every other `_C`
-    wrapper of the model) over the emulation library."""
+    Through the product's own `_C.fastrcnn_loss` / `_C.mask_loss` autograd functions (and every other `_C` wrapper of the
+    model) over the emulation library."""
     from maskrcnn_benchmark.data.synthetic import BatchCollator, SyntheticCOCODataset
     from maskrcnn_benchmark.modeling.detector import build_detection_model
     from maskrcnn_benchmark.modeling.roi_heads.box_head import loss as box_loss
@@ -201,10 +201,9 @@ def test_tiny_mask_rcnn_with_the_fused_head_losses_equals_the_aten_losses(backen
         model = build_detection_model(cfg).train()
         calls = []
         _C._SAMPLER_CALLS[0] = 0      # without a device generator the sampler seeds come from this per-process counter
-        with cpu_shim.install(backend), monkeypatch.context() as mp:
+        with cpu_shim.install("emu-lib"), monkeypatch.context() as mp:
             for name in ("fastrcnn_loss", "mask_loss"):
                 mp.setattr(_C, name, (lambda *a, _fn=getattr(_C, name), _n=name, **k: (calls.append(_n), _fn(*a, **k))[1]))
-            # the emulated sampler's seed counter restarts with every install(): both runs draw the same subsets
             losses = model(images, list(targets))
             sum(v * w for v, w in zip(losses.values(), (1.0, 0.7, 1.3, 0.9, 1.1))).backward()
         assert sorted(calls) == (["fastrcnn_loss", "mask_loss"] if fused else [])
@@ -260,8 +259,7 @@ def test_proposals_and_box_head_sampling_fuzz_device_branches_vs_compositions(se
         # ---- the same modules with the device branches off
         post.fused_decode = False
         monkeypatch.setattr(box_loss, "_FUSED", False)
-        with monkeypatch.context() as mp:
-            mp.setattr(_C, "on_device", lambda t: False)
+        with cpu_shim.install("emu-lib", device_branches=False):
             begin_step()
             rprops = post(anchors, obj, reg, targets)
         assert all(getattr(p, "batch_rows", None) is None for p in rprops)

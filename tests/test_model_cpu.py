@@ -1,7 +1,8 @@
 """Host-logic parity of the model surface against fixtures produced by the REFERENCE's own Python
 modules (tests/golden/make_golden_model.py): anchors, Matcher, BoxList ops, IoU, LevelMapper, target
 assignment (RPN / RetinaNet / Fast R-CNN), RPN loss, mask targets, proposal selection, LR schedule.
-Operators that only exist as HIP kernels are replaced by the oracle through tests/cpu_shim.py."""
+Operators that only exist as HIP kernels are replaced by the oracle through tests/cpu_shim.py, or served by the
+product's own wrappers over the host-emulation library (parameter `cpu-product-wrappers`)."""
 import os
 
 import numpy as np
@@ -31,26 +32,17 @@ def T(a, dev="cpu"):
 
 class _Dev(str):
     """a device string that also names the cpu_shim backend serving the HIP-only operators"""
-    backend = "oracle"
+    backend = "emu-lib"
 
 
-def _emu(backend):
-    d = _Dev("cpu")
-    d.backend = backend
-    return d
-
-
-@pytest.fixture(params=["cpu", pytest.param(_emu("emu-device"), id="cpu-device-branches"),
-                        pytest.param(_emu("emu-lib"), id="cpu-product-wrappers"), pytest.param("cuda", marks=pytest.mark.gpu)])
+@pytest.fixture(params=["cpu", pytest.param(_Dev("cpu"), id="cpu-product-wrappers"), pytest.param("cuda", marks=pytest.mark.gpu)])
 def dev(request):
-    """The reference-generated fixtures are checked four times: on the CPU (host logic; HIP-only operators
-    replaced by the oracle through cpu_shim); on the CPU with the model taking its DEVICE branches (fused label /
-    sampler / sampled-slot / decode launches, served by the HIP sources under the host emulation: cpu_shim backend
-    "emu-device"); on the CPU through the product's own `_C` wrappers over the emulation library (backend "emu-lib":
-    nothing of `_C` replaced); and, in the `-m gpu` suite, on the device through the real HIP kernels (no shim)."""
-    backend = getattr(request.param, "backend", None)
-    if backend in ("emu-device", "emu-lib"):
-        with cpu_shim.install(backend):          # for the whole test: target assignment runs outside `_shim` blocks
+    """The reference-generated fixtures are checked three times: on the CPU (host logic; HIP-only operators
+    replaced by the oracle through cpu_shim); on the CPU through the product's own `_C` wrappers over the emulation
+    library, the model taking its DEVICE branches (fused label / sampler / sampled-slot / decode launches; backend
+    "emu-lib": nothing of `_C` replaced); and, in the `-m gpu` suite, on the device through the real HIP kernels (no shim)."""
+    if isinstance(request.param, _Dev):
+        with cpu_shim.install(request.param.backend):   # for the whole test: target assignment runs outside `_shim` blocks
             yield request.param
     else:
         yield request.param
@@ -511,7 +503,8 @@ def test_do_train_loop_checkpoints_and_resumes(tmp_path, caplog):
 @pytest.mark.parametrize("config", ["e2e_mask_rcnn_R_50_FPN_1x.yaml", "retinanet/retinanet_R-50-FPN_1x.yaml"])
 def test_tiny_model_through_emulated_hip_kernels_matches_oracle_backend(config, monkeypatch):
     """The detector's forward + backward with the detection-head operators served (a) by the oracle and
-    (b) by the HIP kernel sources under the host emulation: same losses and same parameter gradients.
+    (b) by the product's `_C` wrappers over the HIP kernel sources under the host emulation, the model on its host
+    branches as in (a): same losses and same parameter gradients.
     Exercises the kernels with the model's own argument patterns (padded proposal sets, all FPN levels in
     one launch, segmented NMS masks, fused FrozenBN) — without a GPU."""
     import maskrcnn_benchmark.layers.sigmoid_focal_loss as sfl
@@ -527,21 +520,21 @@ def test_tiny_model_through_emulated_hip_kernels_matches_oracle_backend(config, 
     ds = SyntheticCOCODataset(length=2, height=96, width=128, with_masks=cfg.MODEL.MASK_ON, min_objects=2, max_objects=4)
     images, targets, _ = BatchCollator(32)([ds[0], ds[1]])
     results = {}
-    for backend in ("oracle", "emu"):
+    for backend in ("oracle", "emu-lib"):
         torch.manual_seed(0)
         model = build_detection_model(cfg).train()
-        with cpu_shim.install(backend):
+        with cpu_shim.install(backend, device_branches=False):
             torch.manual_seed(1)  # the samplers draw random subsets
             losses = model(images, list(targets))
             sum(losses.values()).backward()
         results[backend] = ({k: float(v) for k, v in losses.items()},
                             [p.grad.clone() for p in model.parameters() if p.grad is not None])
-    lo, le = results["oracle"][0], results["emu"][0]
+    lo, le = results["oracle"][0], results["emu-lib"][0]
     assert lo.keys() == le.keys()
     for k in lo:
         assert abs(lo[k] - le[k]) <= 1e-4 * max(1.0, abs(lo[k])), (k, lo[k], le[k])
-    assert len(results["oracle"][1]) == len(results["emu"][1]) > 10
-    for a, b in zip(results["oracle"][1], results["emu"][1]):
+    assert len(results["oracle"][1]) == len(results["emu-lib"][1]) > 10
+    for a, b in zip(results["oracle"][1], results["emu-lib"][1]):
         assert torch.allclose(a, b, rtol=1e-3, atol=1e-4 * max(1.0, float(a.abs().max())))
 
 

@@ -5,8 +5,9 @@
     `state_dict()` key set and shapes (what utils/model_serialization.py:10-71 matches on) and loads it with strict=True;
   * loss parity — with those weights, the same two-image batch and sampler quotas >= candidates (take-all: no random
     stream enters), every entry of the training loss dict agrees with the reference's within 1e-4 relative — on the CPU
-    (HIP-only operators served by the oracle through tests/cpu_shim.py) and, in the `-m gpu` suite, on the device through the
-    real HIP kernels (ROIAlign, NMS, target kernels, focal loss, fused FrozenBN).
+    (HIP-only operators served by the oracle through tests/cpu_shim.py, and again by the product's own wrappers over the
+    host-emulation library) and, in the `-m gpu` suite, on the device through the real HIP kernels (ROIAlign, NMS, target
+    kernels, focal loss, fused FrozenBN).
 """
 import ast
 import contextlib
@@ -63,16 +64,14 @@ def test_state_dict_keys_equal_the_reference_and_load_strict(name):
 
 
 @pytest.mark.parametrize("name", ["mask_rcnn", "retinanet"])
-@pytest.mark.parametrize("dev", ["cpu", "cpu-device-branches", "cpu-product-wrappers", pytest.param("cuda", marks=pytest.mark.gpu)])
+@pytest.mark.parametrize("dev", ["cpu", "cpu-product-wrappers", pytest.param("cuda", marks=pytest.mark.gpu)])
 def test_losses_equal_the_reference_with_its_weights(name, dev, monkeypatch):
-    # "cpu-device-branches": CPU tensors, but the model takes the branches it takes on the GPU (fused labels / sampler /
-    # sampled-slot targets / proposal decode / batched proposal hand-over), served by the HIP sources under the host emulation
     backend = "oracle"
-    if dev == "cpu-device-branches":
-        dev, backend = "cpu", "emu-device"
     if dev == "cpu-product-wrappers":
-        # the product's own `_C` wrappers and autograd functions, every operator of the model included, over the
-        # host-emulation build of the HIP sources (cpu_shim backend "emu-lib"): nothing of `_C` is replaced
+        # CPU tensors, but the model takes the branches it takes on the GPU (fused labels / sampler / sampled-slot targets /
+        # proposal decode / batched proposal hand-over) through the product's own `_C` wrappers and autograd functions,
+        # every operator of the model included, over the host-emulation build of the HIP sources (cpu_shim backend
+        # "emu-lib"): nothing of `_C` is replaced
         dev, backend = "cpu", "emu-lib"
     cfg, model, ref_sd, il, targets, ref_losses = _build(name, dev)
     model.load_state_dict(ref_sd, strict=True)
