@@ -759,6 +759,28 @@ int detops_frozen_bn_act_backward_nhwc(const void* grad_y, const void* y, const 
                                        int relu, detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 1x1 convolution with the FrozenBatchNorm affine (+ residual) (+ ReLU) as its epilogue (csrc/conv1x1_bn.hip): the
+ * backbone bottleneck's conv1 + bn1, conv3 + bn3 (+ identity) and projection shortcut in ONE launch each, fp32, channels-last:
+ *   y[n, ho, wo, k] = [relu]( (sum_c x[n, ho*stride, wo*stride, c] * w[k, c]) * scale[k] + bias[k] [+ residual[n, ho, wo, k]] )
+ * with Ho = (H - 1) / stride + 1, Wo likewise.  The sum runs on the fp32 matrix units (no reduced-precision mode); the
+ * epilogue rounds like detops_frozen_bn_act_forward_nhwc (product, sum and residual add rounded separately), so the result
+ * differs from convolution + that call only by the convolution's own summation order.
+ *   x [N, H, W, C]; w [K, C] (a [K, C, 1, 1] weight in either memory format); scale, bias [K]; residual (nullable), y
+ *   [N, Ho, Wo, K]; all fp32, dense, 16-byte aligned; groups 1, no padding, no dilation; stride 1 | 2 (2: no residual);
+ *   C % 4 == 0, K % 4 == 0, every tensor below 2^31 elements.
+ *   config: 0 = the library's per-shape routing table, 1 = 64 x 128 tile (32x32x2 MFMA), 2 = 64 x 64 tile (16x16x4 MFMA).
+ * detops_conv1x1_frozen_bn_act_supported -> the tile configuration that serves the shape (1 | 2), or 0: with config 0 also
+ *   when the table keeps the shape on the two-launch path (measured not slower there); always 0 in a build without the
+ *   composable_kernel headers.  Needs a current HIP device.
+ * _forward_nhwc_f32: DETOPS_EUNSUPPORTED with nothing launched for whatever `_supported` answers 0 to and for a misaligned
+ *   pointer.  Puts nothing on the stream but the one kernel launch (no allocation, memset or synchronisation).
+ * ---------------------------------------------------------------------------------------- */
+int detops_conv1x1_frozen_bn_act_supported(int N, int C, int H, int W, int K, int stride, int residual, int config);
+int detops_conv1x1_frozen_bn_act_forward_nhwc_f32(const float* x, const float* w, const float* scale, const float* bias,
+                                                  const float* residual, float* y, int N, int C, int H, int W, int K,
+                                                  int stride, int relu, int config, detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bias (+ ReLU) behind a channels-last convolution (csrc/bias_act.hip) — `conv + bias [+ relu]` of the detector's biased
  * convolutions (reference modeling/backbone/fpn.py:30-40, modeling/rpn/rpn.py:61-76, roi_heads/mask_head): the forward is
  * detops_frozen_bn_act_forward_nhwc with scale 1; the backward is one pass over the gradient:

@@ -1669,6 +1669,57 @@ def frozen_bn_act_backward(grad_y, y, scale, relu, need_residual):
     return gx, gres
 
 
+# ------------------------------------------------------------------------------------------ 1x1 conv + frozen BN
+# A/B switch DETOPS_CONV1X1_BN: "1" (default) the library's routing table decides per shape | "0" every backbone 1x1
+# convolution stays on convolution + frozen_bn_act_forward (two launches) | "t32" / "t16" every shape the kernels serve takes
+# that tile configuration (tests, per-shape measurements).  As a value: None off | 0 routing table | 1 | 2.
+CONV1X1_BN = {"0": None, "1": 0, "t32": 1, "t16": 2}[os.environ.get("DETOPS_CONV1X1_BN", "1")]
+_CONV1X1_BN_ROUTE = {}
+
+
+def conv1x1_bn_config(x, weight, stride, residual=None, config=0):
+    """-> the tile configuration (1 | 2) with which conv1x1_bn_forward serves `conv2d(x, weight, stride=stride)` followed by
+    the FrozenBN epilogue, 0 = the two-launch path runs (not an fp32 channels-last device activation, an autocast region,
+    a shape the kernel does not serve, or — config 0 — one the library's routing table measured no faster)."""
+    if not (x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and weight.dim() == 4 and on_device(x)
+            and x.numel() > 0 and x.is_contiguous(memory_format=torch.channels_last)
+            and weight.shape[2] == 1 and weight.shape[3] == 1 and weight.shape[1] == x.shape[1]
+            and (weight.is_contiguous() or weight.is_contiguous(memory_format=torch.channels_last))
+            and not torch.is_autocast_enabled() and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+            and (residual is None or residual.data_ptr() % 16 == 0)):
+        return 0
+    N, C, H, W = x.shape
+    key = (N, C, H, W, weight.shape[0], stride, residual is not None, config, x.device.index)
+    cfg = _CONV1X1_BN_ROUTE.get(key)
+    if cfg is None:
+        query = getattr(lib, "detops_conv1x1_frozen_bn_act_supported", None)     # (not part of the host emulation build)
+        if query is None:
+            return 0
+        with _on_device(x):
+            cfg = _CONV1X1_BN_ROUTE[key] = int(query(N, C, H, W, weight.shape[0], int(stride), int(residual is not None),
+                                                     int(config)))
+    return cfg
+
+
+def conv1x1_bn_forward(x, weight, scale, bias, residual, relu, stride, config):
+    """Extension: y = [relu](conv2d(x, weight, stride=stride) * scale[k] + bias[k] [+ residual]) in ONE launch
+    (csrc/conv1x1_bn.hip).  `config` is a non-zero answer of conv1x1_bn_config for the same arguments."""
+    _need_cuda("conv1x1_bn_forward", x, weight, scale, bias, residual)
+    N, C, H, W = x.shape
+    K = weight.shape[0]
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    y = torch.empty((N, K, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if residual is not None:
+        if residual.dtype != y.dtype or residual.shape != y.shape:
+            raise RuntimeError("conv1x1_bn_forward: residual must match the output")
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    with _on_device(x), _timed(("conv1x1_bn_fwd[n=%d,C=%d,K=%d,s=%d,res=%d]", (N * Ho * Wo, C, K, stride, residual is not None)), x, every=8):
+        check(lib.detops_conv1x1_frozen_bn_act_forward_nhwc_f32(ptr(x), ptr(weight), ptr(scale), ptr(bias), ptr(residual), ptr(y),
+                                                               N, C, H, W, K, int(stride), int(bool(relu)), int(config),
+                                                               stream_of(x)), "conv1x1_bn_forward")
+    return y
+
+
 _ONES = {}
 
 

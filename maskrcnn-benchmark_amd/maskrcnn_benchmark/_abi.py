@@ -136,6 +136,8 @@ SIGNATURES = {
     "detops_frozen_bn_act_backward": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "detops_frozen_bn_act_forward_nhwc": (c_int, [_P, _P, _P, _P, _P, c_int, ctypes.c_int64, c_int, c_int, _P]),
     "detops_frozen_bn_act_backward_nhwc": (c_int, [_P, _P, _P, _P, _P, c_int, ctypes.c_int64, c_int, c_int, _P]),
+    "detops_conv1x1_frozen_bn_act_supported": (c_int, [c_int] * 8),
+    "detops_conv1x1_frozen_bn_act_forward_nhwc_f32": (c_int, [_P] * 6 + [c_int] * 8 + [_P]),
     "detops_deformable_im2col": (c_int, [_P, _P, _P, _P] + [c_int] * 14 + [_P]),
     "detops_deformable_col2im": (c_int, [_P, _P, _P, _P] + [c_int] * 14 + [_P]),
     "detops_deformable_col2im_workspace_bytes": (c_size_t, [c_int] * 13),

@@ -71,14 +71,15 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         if isinstance(self.bn1, FrozenBatchNorm2d) and x.numel() > 0:
-            # fused affine(+residual)+ReLU: one HIP pass per convolution output (csrc/frozen_bn.hip)
+            # fused affine(+residual)+ReLU: one HIP pass per convolution output (csrc/frozen_bn.hip); behind the 1x1
+            # convolutions it is the convolution kernel's own epilogue where the library serves the shape (csrc/conv1x1_bn.hip)
             if self.downsample is None:
                 identity = x
             else:
-                identity = self.downsample[1].fused(self.downsample[0](x))
-            out = self.bn1.fused(self.conv1(x), relu=True)
+                identity = self.downsample[1].conv1x1_fused(self.downsample[0], x)
+            out = self.bn1.conv1x1_fused(self.conv1, x, relu=True)
             out = self.bn2.fused(self.conv2(out), relu=True)
-            return self.bn3.fused(self.conv3(out), relu=True, residual=identity)
+            return self.bn3.conv1x1_fused(self.conv3, out, relu=True, residual=identity)
         identity = x if self.downsample is None else self.downsample(x)
         out = F.relu_(self.bn1(self.conv1(x)))
         out = F.relu_(self.bn2(self.conv2(out)))
