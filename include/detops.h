@@ -731,6 +731,47 @@ int detops_eval_match(int mode, const double* iou, const int32_t* dt_offset, con
                       detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Batch image preparation (csrc/image_prep.hip; extension: the reference resizes every image on the CPU with
+ * torchvision over Pillow, data/transforms/transforms.py, and copies the padded fp32 batch to the device).  One launch
+ * takes the raw RGB uint8 HWC images of a batch to the zero-padded fp32 batch tensor: Resize, RandomHorizontalFlip,
+ * RandomVerticalFlip, ToTensor, Normalize, to_image_list.
+ *
+ * The resize is Image.resize((ow, oh), Image.BILINEAR) of Pillow, which is integer arithmetic.  For one axis with input
+ * size `in` and output size `out`, all in fp64, nothing contracted:
+ *     scale = in / out;  fs = max(scale, 1.0);  support = 1.0 * fs;  ksize = ceil(support) * 2 + 1;  ss = 1.0 / fs
+ *   and for output index xx:
+ *     center = (xx + 0.5) * scale
+ *     xmin = max(int(center - support + 0.5), 0)             (int: the C cast, truncation toward zero)
+ *     n    = min(int(center + support + 0.5), in) - xmin
+ *     w[x] = max(0, 1 - |(x + xmin - center + 0.5) * ss|)    for x < n
+ *     ww   = the sum of the n weights, added in order;  w[x] = w[x] / ww when ww != 0
+ *     k[x] = int(w[x] * 2^22 + 0.5)
+ *     out[xx] = clip8((2^21 + sum_x in[xmin + x] * k[x]) >> 22)     in 32-bit integers, clip8 to [0, 255]
+ *   The horizontal pass runs first; its uint8 result, rounded and clipped, is the input of the vertical pass.  A pass
+ *   whose axis keeps its size is skipped (the bytes go through unchanged).
+ * After the resize: a horizontal flip (flip bit 0) and a vertical flip (bit 1) mirror the RESIZED image; then
+ *   out[i, c, y, x] = table[c][byte of channel (bgr ? 2 - c : c) at (y, x)]         for y < oh, x < ow, and +0.0 elsewhere.
+ *   table [3, 256] fp32 is made by the caller with the framework's own expressions (t = float32(u8) / 255; t * 255 with
+ *   TO_BGR255; (t - float32(mean[c])) / float32(std[c])), so the batch equals the host pipeline's bit for bit.
+ *
+ *   raw        the images back to back, image i at byte offsets[i] (int64 [N], device), raw_bytes in all
+ *   geom       int32 [N, 5] per image: source h, w, destination oh, ow, flip bits; on the device, and the same records
+ *              on the host as geom_host (the entry point validates them and sizes LDS without a device read)
+ *   out        fp32 [N, 3, Hp, Wp] contiguous, or with channels_last the same tensor in torch.channels_last memory
+ *              ([N, Hp, Wp, 3]).  Every element is written exactly once, the padding zeros included.  16-byte stores where
+ *              a thread's four elements are 16-byte aligned (every row when Wp % 4 == 0), 4-byte stores elsewhere.
+ * THE LARGEST ksize SERVED IS DETOPS_IMAGE_PREP_MAX_KSIZE: a downscale by up to 8 per axis.  A batch with an axis beyond it
+ * returns DETOPS_EINVAL with nothing launched; the caller prepares that batch on the host.
+ * DETOPS_EINVAL also: N < 0 or > 65535, negative sizes, Hp > 65535 * 16, a record with a size < 1 or oh > Hp or ow > Wp,
+ * a null pointer.  N, Hp or Wp == 0 is a no-op.  A record on the device that differs from its host copy cannot make the
+ * kernel leave its buffers: an image it cannot serve is written as zeros.
+ * ---------------------------------------------------------------------------------------- */
+#define DETOPS_IMAGE_PREP_MAX_KSIZE 17
+int detops_image_batch_u8(const uint8_t* raw, int64_t raw_bytes, const int64_t* offsets, const int32_t* geom,
+                          const int32_t* geom_host, int N, const float* table, int bgr, int Hp, int Wp, int channels_last,
+                          float* out, detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused FrozenBatchNorm2d affine (+ residual) (+ ReLU) — the elementwise tail of every backbone
  * convolution: layers/batch_norm.py:19-31 (`x * scale + bias`), then `F.relu_`, and in the
  * bottleneck tail `out += identity; relu` (modeling/backbone/resnet.py:343-366).

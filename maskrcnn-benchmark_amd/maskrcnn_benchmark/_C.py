@@ -921,6 +921,53 @@ def polygons_to_masks(verts, poly_offset, inst_offset, height, width):
     return out
 
 
+# ------------------------------------------------------------------------------------------ batch image preparation
+IMAGE_PREP_MAX_KSIZE = 17             # DETOPS_IMAGE_PREP_MAX_KSIZE: a downscale by up to 8 per axis
+_EINVAL = -1
+
+
+def image_batch(raw, offsets, geom, table, bgr, Hp, Wp, channels_last=False, geom_host=None):
+    """The batch tensor from the raw images of a batch (extension; include/detops.h: detops_image_batch_u8): raw [bytes]
+    uint8 (RGB HWC images back to back), offsets [N] int64 (bytes), geom [N, 5] int32 (source h, w, destination oh, ow, flip
+    bits), table [3, 256] float32 -> float32 [N, 3, Hp, Wp] (torch.channels_last memory with `channels_last`): Pillow's
+    bilinear resize, flips, normalisation and zero padding in one launch.  geom_host: the CPU copy of `geom` when the
+    caller has one (else it is read back).  CPU tensors take the numpy implementation of the same definition
+    (_image_prep_cpu.py); so does, through the host, a device batch with a downscale beyond IMAGE_PREP_MAX_KSIZE."""
+    from . import _image_prep_cpu
+
+    Hp, Wp = int(Hp), int(Wp)
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or offsets.dtype != torch.int64 or geom.dtype != torch.int32 \
+            or geom.dim() != 2 or geom.shape[1] != _image_prep_cpu.GEOM_FIELDS or offsets.numel() != geom.shape[0] \
+            or table.dtype != torch.float32 or tuple(table.shape) != (3, 256) or Hp < 0 or Wp < 0:
+        raise ValueError("image_batch: expected raw [bytes] uint8, offsets [N] int64, geom [N, 5] int32, table [3, 256] float32")
+    tensors = (raw, offsets, geom, table)
+    N = geom.shape[0]
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+
+    def host(device):
+        out = torch.from_numpy(_image_prep_cpu.image_batch(*(t.cpu().numpy() for t in tensors), bool(bgr), Hp, Wp))
+        return out.to(device).contiguous(memory_format=fmt)
+
+    if not any(on_device(t) for t in tensors):
+        return host(raw.device)
+    _need_cuda("image_batch", *tensors)
+    raw, offsets, geom, table = (t.contiguous() for t in tensors)
+    geom_host = (geom.cpu() if geom_host is None else geom_host.to(torch.int32)).contiguous()
+    if geom_host.is_cuda or tuple(geom_host.shape) != tuple(geom.shape):
+        raise ValueError("image_batch: geom_host is the CPU copy of geom")
+    out = torch.empty((N, 3, Hp, Wp), dtype=torch.float32, device=raw.device, memory_format=fmt)
+    if out.numel():
+        with _on_device(raw), _timed(("image_batch[N=%d,%dx%d]", (N, Hp, Wp)), raw):
+            rc = lib.detops_image_batch_u8(ptr(raw), raw.numel(), ptr(offsets), ptr(geom), ptr(geom_host), N, ptr(table),
+                                           int(bool(bgr)), Hp, Wp, int(bool(channels_last)), ptr(out), stream_of(raw))
+        g = geom_host.numpy()
+        if rc == _EINVAL and g[:, :4].min(initial=1) >= 1 and (g[:, 2] <= Hp).all() and (g[:, 3] <= Wp).all() \
+                and max(_image_prep_cpu.axis_ksize(r[a], r[a + 2]) for r in g for a in (0, 1)) > IMAGE_PREP_MAX_KSIZE:
+            return host(raw.device)                   # well-formed, only the downscale is beyond the kernel
+        check(rc, "image_batch")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ detection evaluation
 EVAL_COCO_SEGM, EVAL_COCO_BBOX, EVAL_VOC = 0, 1, 2
 EVAL_MAX_GT = _eval_cpu.MAX_GT        # DETOPS_EVAL_MAX_GT: the largest G_p detops_eval_match serves

@@ -1,0 +1,1 @@
+from .coco import COCODataset  # noqa: F401

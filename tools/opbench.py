@@ -584,6 +584,75 @@ def bench_polygons(C, iters):
     return out
 
 
+def bench_input_prep(C, iters, copy_gbs=None):
+    """the input path of one training batch (csrc/image_prep.hip): two 480 x 640 RGB uint8 images -> 800 x 1066, padded to
+    800 x 1088 (SIZE_DIVISIBILITY 32), the default BGR-255 normalisation, one flipped.
+    image_batch rows: the one launch on a device-resident buffer, HIP events; bytes = the raw images read + the fp32 batch
+    written; frac_of_copy_peak = the bytes WRITTEN over the time, against the copy row of the same run.
+    end-to-end rows (host clock around a device synchronise, per batch): `device` = RawImageBatch.to(cuda) from pinned
+    memory (one 1.8 MB copy + the launch); `host` = the thing it replaces: the host transforms on the same two images
+    (Pillow resize, flip, ToTensor, Normalize), to_image_list, and the 20.9 MB fp32 copy (+ the channels-last pass the
+    detector then runs).  The host rows need Pillow; the image decode is outside both."""
+    from maskrcnn_benchmark.data import transforms as T
+    from maskrcnn_benchmark.data.collate_batch import BatchCollator, RawImageBatch
+    rng = np.random.RandomState(3)
+    yy, xx = np.mgrid[0:480, 0:640]
+    srcs = [np.clip(np.stack([xx * 0.4, yy * 0.5, 128 + 100 * np.sin(0.05 * xx + 0.03 * yy + i)], 2) + rng.normal(0, 20, (480, 640, 3)),
+                    0, 255).astype(np.uint8) for i in range(2)]
+    mean, std, bgr = [102.9801, 115.9465, 122.7717], [1.0, 1.0, 1.0], True
+    table = T.normalisation_table(mean, std, bgr)
+    out = []
+    written = 2 * 3 * 800 * 1088 * 4
+
+    def wall(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e6
+
+    for cl in (False, True):
+        batch = RawImageBatch.pack([T.RawImage(srcs[0], (1066, 800), 0), T.RawImage(srcs[1], (1066, 800), 1)], table, bgr, 32, cl)
+        batch.pin_memory()
+        buf = batch.buffer.cuda()
+        off, geom, tab = buf[:16].view(torch.int64), buf[16:56].view(torch.int32).view(2, 5), buf[56:56 + 3072].view(torch.float32).view(3, 256)
+        us = dev_time_us(lambda: C.image_batch(buf, off, geom, tab, bgr, 800, 1088, channels_last=cl, geom_host=batch.geom), iters)
+        extra = {"bytes_written": written}
+        if copy_gbs:
+            extra["frac_of_copy_peak"] = round(written / us / 1e3 / copy_gbs, 4)
+        out.append(_entry("image_batch 2 x 480x640 -> 800x1066 in 800x1088 %s" % ("channels_last" if cl else "nchw"), us,
+                          buf.numel() + written, extra))
+        us = wall(lambda: batch.to("cuda"), max(iters, 20))
+        out.append(_entry("input_prep end-to-end device (pinned copy + launch) %s" % ("channels_last" if cl else "nchw"), us,
+                          buf.numel() + written, {"h2d_bytes": buf.numel()}))
+    try:
+        from PIL import Image
+    except ImportError:
+        print("input_prep: Pillow is not installed here: the host rows are not measured")
+        return out
+    import random
+    from maskrcnn_benchmark.structures.bounding_box import BoxList
+    pil = [Image.fromarray(a, "RGB") for a in srcs]
+    flips = [T.RandomHorizontalFlip(0.0), T.RandomHorizontalFlip(1.0)]
+    pipes = [T.Compose([T.Resize((800,), 1333), f, T.ToTensor(), T.Normalize(mean, std, bgr)]) for f in flips]
+    box = BoxList(torch.tensor([[10.0, 10.0, 100.0, 100.0]]), (640, 480))
+    collate = BatchCollator(32)
+
+    def host(cl):
+        random.seed(0)
+        items = [pipe(im, box) + (0,) for pipe, im in zip(pipes, pil)]
+        x = collate(items)[0].to("cuda").tensors
+        return x.contiguous(memory_format=torch.channels_last) if cl else x
+
+    for cl in (False, True):
+        us = wall(lambda: host(cl), 10)
+        out.append(_entry("input_prep end-to-end host (Pillow + ToTensor + Normalize + pad + fp32 copy) %s" % ("channels_last" if cl else "nchw"),
+                          us, 2 * 480 * 640 * 3 + written, {"h2d_bytes": written}))
+    return out
+
+
 def bench_evaluation(C, iters):
     """detection evaluation (csrc/evaluate.hip): the 100 pasted detections of bench_masker against the 20 instances of
     bench_polygons, one 800 x 1333 image, all in one category (every pair is a problem pair: one problem of 100 x 20).
@@ -733,6 +802,9 @@ def main():
         res += bench_polygons(C, args.iters)
     if not only or "evaluation" in only:
         res += bench_evaluation(C, args.iters)
+    if not only or "input_prep" in only:
+        copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
+        res += bench_input_prep(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
     if not only or "frozen_bn" in only:
         res += bench_frozen_bn(C, args.iters)
     if not only or "focal" in only:

@@ -5,7 +5,9 @@
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train_net.py ...
 
 One process per GPU; `--local_rank` is accepted for the reference's launcher but LOCAL_RANK from the
-environment (torchrun) wins.  Data is the synthetic COCO-shaped generator (no network / datasets)."""
+environment (torchrun) wins.  DATASETS.TRAIN names starting with `synthetic_` are the synthetic COCO-shaped generator;
+other names are COCO-json datasets of the catalog (config/paths_catalog.py, data root DETOPS_DATA_DIR), prepared on the
+device or the host (DETOPS_INPUT_PREP=device|host)."""
 import argparse
 import logging
 import os
