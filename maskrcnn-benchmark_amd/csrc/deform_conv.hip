@@ -1708,13 +1708,57 @@ col2im_nhwc_gather_kernel(const T* __restrict__ colsG, const int32_t* __restrict
     if (k < nv) vec_store(dst + (k * sub + ls) * V, acc[k]);
 }
 
-// contributions beyond kEllCap per (pixel, tap): added with packed atomics after the gather (rare)
+// contributions beyond kEllCap per (pixel, tap), added after the gather (rare).  A list of up to kOvfReduceMax entries — a few
+// far-displaced corners, or a pile-up on a few pixels — is reduced PER DESTINATION PIXEL in fp32 and added with one rounding: the
+// workgroup of the first entry that names a pixel owns it, sums every entry of that pixel over all taps and updates the pixel's
+// row once (no atomics: one owner per row, and the gather has finished).  Adding entry by entry with packed half atomics rounds
+// every add to the storage type: 72 adds per address for 16 sampling points per tap on one pixel, 3.7e-2 of the gradient's
+// scale in bf16.  The owner search reads e entries for entry e and an owner reads the rest of the list once, 256 lanes wide:
+// at most n / 256 steps per entry, n^2 / 256 in all over the grid (65 k steps at the limit); longer lists keep the atomics,
+// whose cost is linear.  (The list order, and with it the fp32 summation order of a pixel, varies from run to run as before.)
+constexpr int kOvfReduceMax = 4096;
+
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
 col2im_nhwc_overflow_kernel(const T* __restrict__ colsG, const int32_t* __restrict__ ovf_count, const EllOverflow* __restrict__ ovf,
                             int ovf_cap, T* __restrict__ ginT, Geom g) {
+  __shared__ int s_dup, s_nm;
+  __shared__ int s_match[kOvfReduceMax];
   const int n = min(*ovf_count, ovf_cap);
   const int HWo = g.Ho * g.Wo, K = g.kh * g.kw, C = g.C;
+  if (n <= kOvfReduceMax) {
+    for (int e = blockIdx.x; e < n; e += gridDim.x) {   // block-uniform control flow throughout
+      const int32_t li = ovf[e].li;                     // li = b * H * W + pixel (dg == 1)
+      if (threadIdx.x == 0) { s_dup = 0; s_nm = 0; }
+      __syncthreads();
+      for (int j = threadIdx.x; j < e; j += kBlock)
+        if (ovf[j].li == li) s_dup = 1;                 // an earlier entry names the pixel: its workgroup owns it
+      __syncthreads();
+      const bool owner = s_dup == 0;
+      if (owner)                                        // the pixel's entries, this one included
+        for (int j = e + threadIdx.x; j < n; j += kBlock)
+          if (ovf[j].li == li) s_match[atomicAdd(&s_nm, 1)] = j;
+      __syncthreads();
+      if (owner) {
+        const int m = s_nm;
+        for (int c = 2 * threadIdx.x; c < C; c += 2 * kBlock) {
+          float a0 = 0.f, a1 = 0.f;
+          for (int k = 0; k < m; ++k) {
+            const EllOverflow o = ovf[s_match[k]];      // colidx = tap * B * HWo + q
+            const int tap = o.colidx / (g.B * HWo), q = o.colidx - tap * (g.B * HWo);
+            const T* src = colsG + (static_cast<size_t>(q) * K + tap) * C + c;
+            a0 = fmaf(o.w, ld(src), a0);
+            a1 = fmaf(o.w, ld(src + 1), a1);
+          }
+          T* dst = ginT + static_cast<size_t>(li) * C + c;
+          st(dst, ld(dst) + a0);
+          st(dst + 1, ld(dst + 1) + a1);
+        }
+      }
+      __syncthreads();                                  // s_dup, s_nm and the list are reset by the next entry
+    }
+    return;
+  }
   const int half_c = C / 2;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < static_cast<int64_t>(n) * half_c;
        i += static_cast<int64_t>(gridDim.x) * kBlock) {

@@ -2201,14 +2201,22 @@ def _nhwc_forward(input, weight, offset, mask, bias, out, geom):
     Cout = weight.size(0)
     xT = _to_nhwc(input)
     colT = _im2col_nhwc(xT, offset, mask, B, C, H, W, geom)
+    # (a bias goes into the GEMM: sum + bias is rounded to the storage type once, as in the fused kernel's epilogue; added to the
+    #  GEMM's half output it would be rounded twice)
+    bias = None if bias is None else bias.to(out.dtype)
     if is_channels_last(out):
         # channels-last output: ONE GEMM over the whole batch straight into the output's storage ([B*Ho*Wo, Cout])
-        torch.mm(colT, _w_tap_major(weight).t(), out=out.permute(0, 2, 3, 1).reshape(-1, Cout))
+        out2 = out.permute(0, 2, 3, 1).reshape(-1, Cout)
+        if bias is None:
+            torch.mm(colT, _w_tap_major(weight).t(), out=out2)
+        else:
+            torch.addmm(bias, colT, _w_tap_major(weight).t(), out=out2)
     else:
-        torch.bmm(_w_tap_major(weight).unsqueeze(0).expand(B, -1, -1), colT.view(B, -1, colT.size(1)).transpose(1, 2),
-                  out=out.view(B, Cout, -1))
-    if bias is not None:
-        out += bias.to(out.dtype).view(1, -1, 1, 1)
+        w2, cols = _w_tap_major(weight).unsqueeze(0).expand(B, -1, -1), colT.view(B, -1, colT.size(1)).transpose(1, 2)
+        if bias is None:
+            torch.bmm(w2, cols, out=out.view(B, Cout, -1))
+        else:
+            torch.baddbmm(bias.view(1, -1, 1), w2, cols, out=out.view(B, Cout, -1))
     return xT, colT
 
 
@@ -2319,14 +2327,18 @@ def deform_conv_backward_all(input, offset, mask, weight, grad_output, kH, kW, p
     return grad_input, grad_offset, grad_mask, grad_weight, grad_bias
 
 
-def _grouped_weight_times_cols(weight, col, group, out):
-    """out[g] (+)= W[g] @ col[g]; out is [Cout, ncol] (written), fp32/half via rocBLAS/hipBLASLt."""
+def _grouped_weight_times_cols(weight, col, group, out, bias=None):
+    """out[g] = W[g] @ col[g] (+ bias[g] per row); out is [Cout, ncol] (written), fp32/half via rocBLAS/hipBLASLt.  The bias goes
+    into the GEMM: sum + bias is rounded to the storage type once, as in the fused kernel's epilogue."""
     Cout = weight.size(0)
     Mg = Cout // group
     Kg = col.size(0) // group
     w2 = weight.reshape(group, Mg, Kg)
     for g in range(group):
-        torch.mm(w2[g], col[g * Kg:(g + 1) * Kg], out=out[g * Mg:(g + 1) * Mg])
+        if bias is None:
+            torch.mm(w2[g], col[g * Kg:(g + 1) * Kg], out=out[g * Mg:(g + 1) * Mg])
+        else:
+            torch.addmm(bias[g * Mg:(g + 1) * Mg].unsqueeze(1), w2[g], col[g * Kg:(g + 1) * Kg], out=out[g * Mg:(g + 1) * Mg])
 
 
 def _sl(t, sl):
@@ -2351,14 +2363,13 @@ def _dcn_forward(input, weight, offset, mask, bias, output, geom, group, im2col_
             keep.append(kept)
         return
     input, weight = input.contiguous(), weight.contiguous()
+    bias = None if bias is None else bias.to(input.dtype)
     for b0 in range(0, B, im2col_step):
         sl = slice(b0, b0 + im2col_step)
         col = deformable_im2col(input[sl], offset[sl], _sl(mask, sl), *geom)
         buf = torch.empty((Cout, im2col_step * Ho * Wo), dtype=input.dtype, device=input.device)
-        _grouped_weight_times_cols(weight, col, group, buf)
+        _grouped_weight_times_cols(weight, col, group, buf, bias)
         out[sl].copy_(buf.view(Cout, im2col_step, Ho, Wo).transpose(0, 1))
-    if bias is not None:
-        out += bias.view(1, -1, 1, 1)
 
 
 def _ref_backward_input(input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, geom, group, im2col_step):
