@@ -845,6 +845,32 @@ int detops_column_sum_f32(const float* x, float* out, int64_t rows, int C, void*
 int detops_column_sum(const void* x, float* out, int dtype, int64_t rows, int C, void* workspace, size_t workspace_bytes,
                       detops_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GroupNorm (+ residual) (+ ReLU) on channels-last activations (csrc/group_norm.hip) — the normalisation of the reference's
+ * gn_baselines models (modeling/make_layers.py:24-39, backbone/resnet.py BottleneckWithGN / StemWithGN).
+ *   x, residual (nullable), y, grad_*: [N, HW, C], the channel the fastest index; dtype code as above (fp32 arithmetic)
+ *   G groups of C / G ADJACENT channels; gamma, beta (nullable: 1 / 0), grad_gamma, grad_beta: fp32 [C]
+ *   mean, rstd: fp32 [N, G], rstd = 1 / sqrt(var + eps) with the biased variance of the group's HW * C / G elements
+ *   forward : y = [relu]( (x - mean[n, g]) * rstd[n, g] * gamma[c] + beta[c] [+ residual] )
+ *   backward: g = relu ? (y > 0 ? grad_y : 0) : grad_y  (y is read only with relu);  grad_residual (nullable) = g;
+ *             grad_x = rstd * (gamma * g - mean_group(gamma * g) - xhat * mean_group(gamma * g * xhat));
+ *             grad_gamma[c] = sum g * xhat, grad_beta[c] = sum g  (each nullable: not wanted)
+ * The variance comes from (count, mean, M2) triples merged by Chan's formula in a fixed order, never from a sum of
+ * squares; no atomics: two calls give identical bits.  Any pointer alignment (narrower vectors below 16 bytes).
+ * detops_group_norm_supported: 1 when C % G == 0 and C / G is a power of two <= 256, else 0.  An unserved (C, G) returns
+ * DETOPS_EUNSUPPORTED with nothing launched; N == 0 or HW == 0 returns 0 with nothing launched or written.
+ * workspace: >= detops_group_norm_workspace_bytes(N, HW, C, G) bytes (serves either direction), else DETOPS_EWORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+int detops_group_norm_supported(int C, int G);
+size_t detops_group_norm_workspace_bytes(int N, int64_t HW, int C, int G);
+int detops_group_norm_forward_nhwc(const void* x, const float* gamma, const float* beta, const void* residual, void* y,
+                                   float* mean, float* rstd, int dtype, int N, int64_t HW, int C, int G, float eps, int relu,
+                                   void* workspace, size_t workspace_bytes, detops_stream_t stream);
+int detops_group_norm_backward_nhwc(const void* grad_y, const void* x, const void* y, const float* gamma, const float* mean,
+                                    const float* rstd, void* grad_x, void* grad_residual, float* grad_gamma, float* grad_beta,
+                                    int dtype, int N, int64_t HW, int C, int G, int relu, void* workspace,
+                                    size_t workspace_bytes, detops_stream_t stream);
+
 /* RPN loss in one pass over the head outputs (reference modeling/rpn/loss.py:92-127 with
  * modeling/box_coder.py:27-51 and modeling/rpn/utils.py:9-45): objectness = BCE-with-logits over the sampled
  * anchors, box = smooth-L1(beta) against BoxCoder.encode(matched gt, anchor) over the sampled positives, both

@@ -1716,6 +1716,84 @@ def frozen_bn_act_backward(grad_y, y, scale, relu, need_residual):
     return gx, gres
 
 
+# ------------------------------------------------------------------------------------------ group norm
+# A/B switch DETOPS_GROUP_NORM: "fused" (default) channels-last GroupNorm (+ residual) (+ ReLU) runs in csrc/group_norm.hip |
+# "torch" every GroupNorm layer calls F.group_norm (+ add) (+ relu).  Read once at import; layers.GroupNorm asks it per call.
+GROUP_NORM = os.environ.get("DETOPS_GROUP_NORM", "fused")
+if GROUP_NORM not in ("fused", "torch"):
+    raise RuntimeError("DETOPS_GROUP_NORM must be 'fused' or 'torch', got %r" % GROUP_NORM)
+
+
+GROUP_NORM_MAX_GROUP_WIDTH = 256      # kGnMaxD of csrc/group_norm.hip
+
+
+def group_norm_serves(C, G):
+    """the rule of detops_group_norm_supported, answered on the host (the routing of a layer that the library does not
+    serve costs no library call; tests/test_group_norm_gpu.py holds the two against each other)"""
+    D = C // G if G > 0 and C % G == 0 else 0
+    return 0 < D <= GROUP_NORM_MAX_GROUP_WIDTH and D & (D - 1) == 0
+
+
+def group_norm_supported(x, G):
+    """True when group_norm_forward serves `x` with G groups: a non-empty fp32 / fp16 / bf16 channels-last 4-d device
+    activation whose (C, G) the library serves (C % G == 0, a power-of-two group width of at most 256 channels)."""
+    return (on_device(x) and x.dtype in _lib.DTYPE_CODE and is_channels_last(x) and x.numel() > 0
+            and group_norm_serves(int(x.shape[1]), int(G)) and hasattr(lib, "detops_group_norm_forward_nhwc"))
+
+
+def _gn_workspace(x, N, HW, C, G):
+    nbytes = int(lib.detops_group_norm_workspace_bytes(N, HW, C, G))
+    return torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device), nbytes
+
+
+def group_norm_forward(x, G, gamma, beta, eps, residual, relu):
+    """Extension: (y, mean, rstd) with y = [relu](group_norm(x, G, gamma, beta, eps) [+ residual]) for a channels-last
+    [N, C, H, W] activation, in the storage dtype of `x`; mean / rstd are fp32 [N, G].  gamma / beta: fp32 [C] or None."""
+    _need_cuda("group_norm_forward", x, gamma, beta, residual)
+    if not is_channels_last(x):
+        raise RuntimeError("group_norm_forward: expected a channels-last 4-d activation")
+    code = _lib.DTYPE_CODE[x.dtype]
+    N, C = int(x.shape[0]), int(x.shape[1])
+    HW = int(x.shape[2]) * int(x.shape[3])
+    if residual is not None:
+        if residual.dtype != x.dtype or residual.shape != x.shape:
+            raise RuntimeError("group_norm_forward: residual must match x")
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    gamma = None if gamma is None else _f32c("group_norm_forward", gamma)
+    beta = None if beta is None else _f32c("group_norm_forward", beta)
+    y = torch.empty_like(x)      # preserves the memory format
+    mean = torch.empty((N, G), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((N, G), dtype=torch.float32, device=x.device)
+    ws, nbytes = _gn_workspace(x, N, HW, C, G)
+    with _on_device(x), _timed(("group_norm_fwd[n=%d,C=%d,G=%d,e=%d,res=%d]", (x.numel(), C, G, _ESIZE[x.dtype], residual is not None)), x, every=8):
+        check(lib.detops_group_norm_forward_nhwc(ptr(x), ptr(gamma), ptr(beta), ptr(residual), ptr(y), ptr(mean), ptr(rstd), code,
+                                                 N, HW, C, int(G), float(eps), int(bool(relu)), ptr(ws), nbytes, stream_of(x)),
+              "group_norm_forward")
+    return y, mean, rstd
+
+
+def group_norm_backward(grad_y, x, y, G, gamma, mean, rstd, relu, need_residual, need_gamma, need_beta):
+    """Extension: (grad_x, grad_residual or None, grad_gamma or None, grad_beta or None) of group_norm_forward.  `y` (the
+    forward's output) is read only with relu.  Deterministic."""
+    _need_cuda("group_norm_backward", grad_y, x, gamma, mean, rstd)
+    code = _lib.DTYPE_CODE[x.dtype]
+    if grad_y.dtype != x.dtype:
+        grad_y = grad_y.to(x.dtype)
+    grad_y = grad_y.contiguous(memory_format=torch.channels_last)
+    N, C = int(x.shape[0]), int(x.shape[1])
+    HW = int(x.shape[2]) * int(x.shape[3])
+    gx = torch.empty_like(x)
+    gres = torch.empty_like(x) if need_residual else None
+    ggamma = torch.empty((C,), dtype=torch.float32, device=x.device) if need_gamma else None
+    gbeta = torch.empty((C,), dtype=torch.float32, device=x.device) if need_beta else None
+    ws, nbytes = _gn_workspace(x, N, HW, C, G)
+    with _on_device(x), _timed(("group_norm_bwd[n=%d,C=%d,G=%d,e=%d,relu=%d]", (x.numel(), C, G, _ESIZE[x.dtype], bool(relu))), x, every=8):
+        check(lib.detops_group_norm_backward_nhwc(ptr(grad_y), ptr(x), ptr(y) if relu else None, ptr(gamma), ptr(mean), ptr(rstd),
+                                                  ptr(gx), ptr(gres), ptr(ggamma), ptr(gbeta), code, N, HW, C, int(G),
+                                                  int(bool(relu)), ptr(ws), nbytes, stream_of(x)), "group_norm_backward")
+    return gx, gres, ggamma, gbeta
+
+
 # ------------------------------------------------------------------------------------------ 1x1 conv + frozen BN
 # A/B switch DETOPS_CONV1X1_BN: "1" (default) the library's routing table decides per shape | "0" every backbone 1x1
 # convolution stays on convolution + frozen_bn_act_forward (two launches) | "t32" / "t16" every shape the kernels serve takes

@@ -99,6 +99,10 @@ SIGNATURES = {
     "detops_column_sum": (c_int, [_P, _P, c_int, ctypes.c_int64, c_int, _P, c_size_t, _P]),
     "detops_column_sum_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int]),
     "detops_column_sum_f32": (c_int, [_P, _P, ctypes.c_int64, c_int, _P, c_size_t, _P]),
+    "detops_group_norm_supported": (c_int, [c_int, c_int]),
+    "detops_group_norm_workspace_bytes": (c_size_t, [c_int, ctypes.c_int64, c_int, c_int]),
+    "detops_group_norm_forward_nhwc": (c_int, [_P] * 7 + [c_int, c_int, ctypes.c_int64, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
+    "detops_group_norm_backward_nhwc": (c_int, [_P] * 10 + [c_int, c_int, ctypes.c_int64, c_int, c_int, c_int, _P, c_size_t, _P]),
     "detops_roi_align_forward_f64": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int, _P]),
     "detops_roi_align_backward_f64": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_float, c_int, c_int, _P]),
     "detops_roi_pool_forward_f64": (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [c_float, _P]),

@@ -1,5 +1,6 @@
 """Operator API of the reference (maskrcnn_benchmark/layers/__init__.py:23-46), same names."""
 from .batch_norm import FrozenBatchNorm2d
+from .group_norm import GroupNorm  # this project's addition: importable, not in __all__ (which mirrors the reference's list)
 from .misc import Conv2d
 from .misc import DFConv2d
 from .misc import ConvTranspose2d

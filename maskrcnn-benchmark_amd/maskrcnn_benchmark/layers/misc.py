@@ -59,6 +59,8 @@ def conv_bias_act(conv, x, relu=False):
             return _C.bias_act(y, conv.bias, relu)
         y = y + conv.bias.to(y.dtype).view(1, -1, 1, 1)
         return torch.relu(y) if relu else y
+    if relu and type(conv).__name__ == "ConvNormAct":      # conv + GroupNorm block (modeling/make_layers.py): the ReLU joins its launch
+        return conv(x, relu=True)
     y = conv(x)
     return torch.relu(y) if relu else y
 

@@ -5,7 +5,7 @@ from collections import OrderedDict
 from torch import nn
 
 from maskrcnn_benchmark.modeling import registry
-from maskrcnn_benchmark.modeling.make_layers import conv_with_kaiming_uniform
+from maskrcnn_benchmark.modeling.make_layers import building, conv_with_kaiming_uniform
 
 from . import fpn as fpn_module
 from . import resnet
@@ -54,4 +54,5 @@ def build_backbone(cfg):
     name = cfg.MODEL.BACKBONE.CONV_BODY
     assert name in registry.BACKBONES, \
         "cfg.MODEL.BACKBONE.CONV_BODY: {} is not registered in registry".format(name)
-    return registry.BACKBONES[name](cfg)
+    with building(cfg):      # GroupNorm layers take MODEL.GROUP_NORM from THIS cfg, not from the global one
+        return registry.BACKBONES[name](cfg)

@@ -7,7 +7,7 @@ from collections import namedtuple
 import torch.nn.functional as F
 from torch import nn
 
-from maskrcnn_benchmark.layers import Conv2d, DFConv2d, FrozenBatchNorm2d
+from maskrcnn_benchmark.layers import Conv2d, DFConv2d, FrozenBatchNorm2d, GroupNorm
 from maskrcnn_benchmark.modeling.make_layers import group_norm
 
 StageSpec = namedtuple("StageSpec", ["index", "block_count", "return_features"])
@@ -80,6 +80,13 @@ class Bottleneck(nn.Module):
             out = self.bn1.conv1x1_fused(self.conv1, x, relu=True)
             out = self.bn2.fused(self.conv2(out), relu=True)
             return self.bn3.conv1x1_fused(self.conv3, out, relu=True, residual=identity)
+        if isinstance(self.bn1, GroupNorm) and x.numel() > 0:
+            # GroupNorm (+ residual) (+ ReLU) in one launch per convolution output where csrc/group_norm.hip serves it
+            # (channels-last on the device); GroupNorm.fused composes F.group_norm, `+=` and relu_ as below everywhere else
+            identity = x if self.downsample is None else self.downsample[1].fused(self.downsample[0](x))
+            out = self.bn1.fused(self.conv1(x), relu=True)
+            out = self.bn2.fused(self.conv2(out), relu=True)
+            return self.bn3.fused(self.conv3(out), relu=True, residual=identity)
         identity = x if self.downsample is None else self.downsample(x)
         out = F.relu_(self.bn1(self.conv1(x)))
         out = F.relu_(self.bn2(self.conv2(out)))
@@ -115,7 +122,7 @@ class Stem(nn.Module):
         _kaiming(self.conv1)
 
     def forward(self, x):
-        if isinstance(self.bn1, FrozenBatchNorm2d) and x.numel() > 0:
+        if isinstance(self.bn1, (FrozenBatchNorm2d, GroupNorm)) and x.numel() > 0:
             x = self.bn1.fused(self.conv1(x), relu=True)
         else:
             x = F.relu_(self.bn1(self.conv1(x)))

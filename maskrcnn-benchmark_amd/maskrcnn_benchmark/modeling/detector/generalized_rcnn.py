@@ -32,7 +32,8 @@ class GeneralizedRCNN(nn.Module):
         follow the tensor's layout.  `heads=False`: the pyramid is handed to the RPN / ROI heads as NCHW (one conversion
         per level).  `heads=True`: the heads take the channels-last pyramid as it is — the RPN head's convolutions run
         channels-last (its two small outputs are handed to the proposal / loss kernels as NCHW), the poolers read the
-        pyramid in place (csrc/roi_align_nhwc.hip), the box head's pooled tensor stays [K, C, 7, 7] for its FC layers and
+        pyramid in place (csrc/roi_align_nhwc.hip), the MLP box head's pooled tensor stays [K, C, 7, 7] for its FC layers (the
+        convolutional box head, FPNXconv1fcFeatureExtractor, runs channels-last up to its FC layer) and
         the mask and keypoint heads (pooler output, convolutions, deconvolution) run channels-last.  Parameters, buffers and the
         state_dict are untouched (a memory format is a stride permutation, not a shape)."""
         fmt = torch.channels_last if on else torch.contiguous_format
@@ -50,6 +51,14 @@ class GeneralizedRCNN(nn.Module):
                 mask.feature_extractor.to(memory_format=hfmt)
                 mask.predictor.to(memory_format=hfmt)
                 mask.feature_extractor.pooler.output_channels_last = heads
+        box = self.roi_heads["box"] if (self.roi_heads and "box" in self.roi_heads) else None
+        if box is not None and type(box.feature_extractor).__name__ == "FPNXconv1fcFeatureExtractor" \
+                and any(type(m).__name__ == "GroupNorm" for m in box.feature_extractor.xconvs):
+            # the convolutional box head with GroupNorm: pooled tensor and the stacked convolutions channels-last (the GroupNorm
+            # layers then run csrc/group_norm.hip); its forward flattens to the NCHW element order in front of fc6.  Without
+            # GroupNorm the head stays NCHW, as before.
+            box.feature_extractor.xconvs.to(memory_format=hfmt)
+            box.feature_extractor.pooler.output_channels_last = heads
         keypoint = self.roi_heads["keypoint"] if (self.roi_heads and "keypoint" in self.roi_heads) else None
         if keypoint is not None:
             keypoint.feature_extractor.to(memory_format=hfmt)

@@ -1,10 +1,26 @@
 """Layer factories with the reference's initialisation (reference modeling/make_layers.py:13-123)."""
+import contextlib
+
 import torch
 from torch import nn
 from torch.nn import functional as F
 
 from maskrcnn_benchmark.config import cfg
-from maskrcnn_benchmark.layers import Conv2d
+from maskrcnn_benchmark.layers import Conv2d, GroupNorm
+
+# the cfg a model is being built from (build_detection_model / build_backbone set it around construction): group_norm() has
+# no cfg argument in the reference's signature and would otherwise read the GLOBAL cfg, ignoring MODEL.GROUP_NORM.* of a yaml
+# or a command line merged into a clone (engine/bench_step.py::load_cfg)
+_BUILDING_CFG = [None]
+
+
+@contextlib.contextmanager
+def building(build_cfg):
+    outer, _BUILDING_CFG[0] = _BUILDING_CFG[0], build_cfg
+    try:
+        yield
+    finally:
+        _BUILDING_CFG[0] = outer
 
 
 def get_group_gn(dim, dim_per_gp, num_groups):
@@ -18,11 +34,33 @@ def get_group_gn(dim, dim_per_gp, num_groups):
 
 
 def group_norm(out_channels, affine=True, divisor=1):
+    gn = (_BUILDING_CFG[0] or cfg).MODEL.GROUP_NORM      # outside a build: the global cfg, as in the reference
     out_channels = out_channels // divisor
-    dim_per_gp = cfg.MODEL.GROUP_NORM.DIM_PER_GP // divisor
-    num_groups = cfg.MODEL.GROUP_NORM.NUM_GROUPS // divisor
-    return nn.GroupNorm(get_group_gn(out_channels, dim_per_gp, num_groups), out_channels,
-                        cfg.MODEL.GROUP_NORM.EPSILON, affine)
+    dim_per_gp = gn.DIM_PER_GP // divisor
+    num_groups = gn.NUM_GROUPS // divisor
+    return GroupNorm(get_group_gn(out_channels, dim_per_gp, num_groups), out_channels, gn.EPSILON, affine)
+
+
+class ConvNormAct(nn.Sequential):
+    """conv, GroupNorm [, ReLU] with the reference's child indices (state_dict keys `0.weight`, `1.weight`, `1.bias`).  Where
+    the GroupNorm kernel serves the convolution's output, normalisation and ReLU are ONE launch; the ReLU module stays
+    registered (it has no parameters).  Otherwise the children run one after another, as in nn.Sequential."""
+
+    def forward(self, x, relu=False):
+        """`relu`: one more ReLU behind the block (the mask head applies it outside a ReLU-free block)"""
+        y = self[0](x)
+        gn = self[1]
+        if isinstance(gn, GroupNorm) and gn.serves(y):
+            return gn.fused(y, relu=relu or len(self) > 2)
+        for m in list(self)[1:]:
+            y = m(y)
+        return torch.relu(y) if relu else y
+
+
+def _block(layers):
+    if len(layers) == 1:
+        return layers[0]
+    return ConvNormAct(*layers) if isinstance(layers[1], GroupNorm) else nn.Sequential(*layers)
 
 
 def make_conv3x3(in_channels, out_channels, dilation=1, stride=1, use_gn=False, use_relu=False,
@@ -40,7 +78,7 @@ def make_conv3x3(in_channels, out_channels, dilation=1, stride=1, use_gn=False, 
         layers.append(group_norm(out_channels))
     if use_relu:
         layers.append(nn.ReLU(inplace=True))
-    return nn.Sequential(*layers) if len(layers) > 1 else conv
+    return _block(layers)
 
 
 def make_fc(dim_in, hidden_dim, use_gn=False):
@@ -64,6 +102,6 @@ def conv_with_kaiming_uniform(use_gn=False, use_relu=False):
             layers.append(group_norm(out_channels))
         if use_relu:
             layers.append(nn.ReLU(inplace=True))
-        return nn.Sequential(*layers) if len(layers) > 1 else conv
+        return _block(layers)
 
     return make_conv

@@ -2,6 +2,7 @@
 from torch import nn
 from torch.nn import functional as F
 
+from maskrcnn_benchmark.layers import GroupNorm
 from maskrcnn_benchmark.modeling import registry
 from maskrcnn_benchmark.modeling.backbone import resnet
 from maskrcnn_benchmark.modeling.make_layers import group_norm, make_fc
@@ -70,7 +71,19 @@ class FPNXconv1fcFeatureExtractor(nn.Module):
         self.out_channels = H.MLP_HEAD_DIM
 
     def forward(self, x, proposals):
-        x = self.xconvs(self.pooler(x, proposals))
+        """The pooled tensor and the convolutions follow `pooler.output_channels_last` (GeneralizedRCNN.set_channels_last with
+        heads=True: the GroupNorm layers then meet their kernel, each with its ReLU in the same launch); `flatten` hands fc6
+        the NCHW element order its weights are in — one conversion of [K, C, 7, 7] — whatever the layout."""
+        x = self.pooler(x, proposals)
+        mods = list(self.xconvs)
+        i = 0
+        while i < len(mods):
+            x = mods[i](x)
+            nxt = mods[i + 1:i + 3]
+            if len(nxt) == 2 and isinstance(nxt[0], GroupNorm) and isinstance(nxt[1], nn.ReLU) and nxt[0].serves(x):
+                x = nxt[0].fused(x, relu=True)
+                i += 2
+            i += 1
         return F.relu(self.fc6(x.flatten(1)))
 
 

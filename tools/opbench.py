@@ -304,6 +304,53 @@ def bench_frozen_bn(C, iters):
     return out
 
 
+def bench_group_norm(C, iters, copy_gbs=None):
+    """channels-last GroupNorm + residual + ReLU: the fused kernels (csrc/group_norm.hip, through layers.GroupNorm) against
+    F.group_norm + add + relu on the SAME channels-last tensors, forward and forward + backward, fp32 and bf16, at the GN
+    baselines' shapes (backbone res2-res5 stages at 2 images, box head 1024 ROIs, mask head 128 ROIs).  Bytes: what the
+    algorithm must move — forward x, residual, y (3 tensors); backward grad_y, x, y, grad_x, grad_residual (5 more);
+    frac_of_copy = those bytes over the time, against the copy row of the same run."""
+    import torch.nn.functional as F
+    from maskrcnn_benchmark.layers import GroupNorm
+    out = []
+    shapes = [("backbone", (2, 64, 400, 672)), ("backbone", (2, 256, 200, 336)), ("backbone", (2, 512, 100, 168)),
+              ("backbone", (2, 2048, 25, 42)), ("box head", (1024, 256, 7, 7)), ("mask head", (128, 256, 14, 14))]
+    for where, shape in shapes:
+        for dtype in (torch.float32, torch.bfloat16):
+            gn = GroupNorm(32, shape[1]).cuda()
+            x = torch.randn(shape, device="cuda").to(dtype).contiguous(memory_format=torch.channels_last)
+            r = torch.randn(shape, device="cuda").to(dtype).contiguous(memory_format=torch.channels_last)
+            gy = torch.randn(shape, device="cuda").to(dtype).contiguous(memory_format=torch.channels_last)
+            assert gn.serves(x)
+            nb = x.numel() * x.element_size()
+            xg, rg = x.clone().requires_grad_(True), r.clone().requires_grad_(True)
+
+            def torch_fwd(a, b):      # half storage: as the model runs it, under autocast (ATen's group_norm then works in fp32)
+                with torch.autocast("cuda", dtype=dtype, enabled=dtype != torch.float32):
+                    return torch.relu(F.group_norm(a, gn.num_groups, gn.weight, gn.bias, gn.eps) + b)
+
+            def both(f):
+                xg.grad = rg.grad = gn.weight.grad = gn.bias.grad = None
+                y = f(xg, rg)
+                y.backward(gy.to(y.dtype))
+
+            rows = {}
+            with torch.no_grad():
+                rows["fwd fused"] = (dev_time_us(lambda: gn.fused(x, True, r), iters), 3 * nb)
+                rows["fwd torch"] = (dev_time_us(lambda: torch_fwd(x, r), iters), 3 * nb)
+            rows["fwd+bwd fused"] = (dev_time_us(lambda: both(lambda a, b: gn.fused(a, True, b)), iters), 8 * nb)
+            rows["fwd+bwd torch"] = (dev_time_us(lambda: both(torch_fwd), iters), 8 * nb)
+            tag = "group_norm+add+relu %s %s %s" % (where, "x".join(map(str, shape)), str(dtype)[6:])
+            for kind in ("fwd", "fwd+bwd"):
+                for impl in ("fused", "torch"):
+                    us, alg = rows["%s %s" % (kind, impl)]
+                    extra = {"speedup_vs_torch": round(rows[kind + " torch"][0] / us, 2)} if impl == "fused" else {}
+                    if copy_gbs:
+                        extra["frac_of_copy"] = round(alg / us / 1e3 / copy_gbs, 4)
+                    out.append(_entry("%s %s %s" % (tag, kind, impl), us, alg, extra))
+    return out
+
+
 def bench_focal(C, iters):
     out = []
     for R in (200000, 403200):
@@ -807,6 +854,9 @@ def main():
         res += bench_input_prep(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
     if not only or "frozen_bn" in only:
         res += bench_frozen_bn(C, args.iters)
+    if not only or "group_norm" in only:
+        copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
+        res += bench_group_norm(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
     if not only or "focal" in only:
         res += bench_focal(C, args.iters)
     if not only or "dcn" in only:
