@@ -5,6 +5,7 @@
 // csrc/cpu/ROIAlign_cpu.cpp:242).  No configuration of the training path uses double, so these are plain API-completeness
 // kernels — one thread per output element, the reference's arithmetic in T = double operation by operation, hardware fp64
 // atomics (global_atomic_add_f64) for the two scatters — not tuned: the fp32 kernels of this library are the product.
+#include <float.h>
 #include <algorithm>
 
 #include "detops_common.h"
@@ -58,8 +59,10 @@ roi_align_fwd_f64_kernel(const double* __restrict__ in, const double* __restrict
     double acc = 0.;
     for (int iy = 0; iy < g.gh; ++iy) {
       const TapD y = axis_d(g.sh, g.bh, ph, iy, g.gh, H);
+      if (y.l == 0. && y.h == 0.) continue;     // outside the map: 0 without reading (ROIAlign_cuda.cu:22-25), not 0 * d[0]
       for (int ix = 0; ix < g.gw; ++ix) {
         const TapD x = axis_d(g.sw, g.bw, pw, ix, g.gw, W);
+        if (x.l == 0. && x.h == 0.) continue;
         const double w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;
         acc += w1 * d[y.lo * W + x.lo] + w2 * d[y.lo * W + x.hi] + w3 * d[y.hi * W + x.lo] + w4 * d[y.hi * W + x.hi];
       }
@@ -115,7 +118,7 @@ roi_pool_fwd_f64_kernel(const double* __restrict__ in, const double* __restrict_
     hs = min(max(hs + rsh, 0), H); he = min(max(he + rsh, 0), H);
     ws = min(max(ws + rsw, 0), W); we = min(max(we + rsw, 0), W);
     const bool empty = (he <= hs) || (we <= ws);
-    double mv = empty ? 0. : -1.7976931348623157e308;      // the reference starts at -FLT_MAX; any finite input beats either
+    double mv = empty ? 0. : -static_cast<double>(FLT_MAX);  // the reference starts at -FLT_MAX for every T (ROIPool_cuda.cu:60)
     int mi = -1;
     const double* d = in + (static_cast<int64_t>(b) * C + c) * H * W;
     for (int h = hs; h < he; ++h)

@@ -83,11 +83,15 @@ roi_align_fwd_kernel(Levels L, const float* __restrict__ rois, const int32_t* __
     for (int iy = 0; iy < g.gh; ++iy) {
       const Tap ty = use_tab ? tabY[ph * g.gh + iy]
                              : axis_entry(g.start_h, g.bin_h, ph, iy, g.gh, H, W);
+      // a sample outside the map counts as 0 and reads nothing (ROIAlign_cuda.cu:22-25): 0 * pixel 0 is not 0 when that
+      // pixel holds Inf or NaN.  On a finite map skipping gives the same bits: the sum starts at +0.f.
+      if (ty.l == 0.f && ty.h == 0.f) continue;
       const float* r0 = d + ty.lo;
       const float* r1 = d + ty.hi;
       for (int ix = 0; ix < g.gw; ++ix) {
         const Tap tx = use_tab ? tabX[pw * g.gw + ix]
                                : axis_entry(g.start_w, g.bin_w, pw, ix, g.gw, W, 1);
+        if (tx.l == 0.f && tx.h == 0.f) continue;
         const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
         const float v1 = r0[tx.lo], v2 = r0[tx.hi], v3 = r1[tx.lo], v4 = r1[tx.hi];
         acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
@@ -105,7 +109,10 @@ roi_align_fwd_kernel(Levels L, const float* __restrict__ rois, const int32_t* __
 //     bilinear weights live in registers for the whole channel loop;
 //   * taps are addressed as (lo, lo+1): the patch carries one extra row/column that replicates the clamped
 //     border pixel, which is exactly what the reference reads when x_high == x_low (weight 0 on that tap);
-//   * reference operation order, FP contraction off: bit-identical to the reference CPU kernel.
+//   * reference operation order, FP contraction off: bit-identical to the reference CPU kernel;
+//   * a sample outside the map has four zero weights on patch offset 0, the first pixels of the ROI's OWN footprint: it
+//     adds 0 as long as those are finite.  (The kernels that gather straight from the map skip such samples instead:
+//     their table entry points at pixel 0 of the plane, which no sample of the ROI may touch.)
 // Footprints that do not fit the LDS budget fall through to direct gathers inside the same kernel.
 // ------------------------------------------------------------------------------------------
 constexpr int kFwdDmaWps = 5;  // waves per SIMD the register budget must allow (no staging registers)
@@ -317,10 +324,12 @@ roi_align_fwd_dma_kernel(Levels L, const float* __restrict__ rois, const int32_t
       float acc = 0.f;
       for (int iy = 0; iy < SR; ++iy) {
         const Tap ty = tabY[ph * SR + iy];
+        if (ty.l == 0.f && ty.h == 0.f) continue;   // outside the map: nothing is read (see roi_align_fwd_kernel)
         const float* r0 = d + ty.lo * W;
         const float* r1 = d + ty.hi * W;
         for (int ix = 0; ix < SR; ++ix) {
           const Tap tx = tabX[pw * SR + ix];
+          if (tx.l == 0.f && tx.h == 0.f) continue;
           const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4_ = ty.l * tx.l;
           acc += w1 * r0[tx.lo] + w2 * r0[tx.hi] + w3 * r1[tx.lo] + w4_ * r1[tx.hi];
         }

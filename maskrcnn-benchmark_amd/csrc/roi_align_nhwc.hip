@@ -59,6 +59,37 @@ roi_nhwc_order_kernel(Levels L, const float* __restrict__ rois, const int32_t* _
   roi_order_role(L, rois, levels_in, K, order, keys, static_cast<int>(blockIdx.x));
 }
 
+// The samples of one bin, reference order of operations.  A sample outside the map counts as 0 and reads nothing
+// (ROIAlign_cuda.cu:22-25); its table entry has both weights 0 and points at pixel 0, and 0 * pixel 0 is not 0 when that pixel
+// holds Inf or NaN.  kSkip = true steps over such samples (same bits on a finite map: the sum starts at +0.f); kSkip = false
+// is the branch-free loop for the ROIs that have none.
+__device__ __forceinline__ bool nf_outside(const Tap& t) { return t.l == 0.f && t.h == 0.f; }   // a tap in range has h = 1 - l
+
+template <int V, bool kSkip>
+__device__ __forceinline__ void nf_bin_sum(float (&acc)[V], const Tap* tabY, const Tap* tabX, bool use_tab, const RoiGeom& g,
+                                           int ph, int pw, int H, int W, int C, const float* __restrict__ base) {
+#pragma clang fp contract(off)
+  for (int iy = 0; iy < g.gh; ++iy) {
+    const Tap ty = use_tab ? tabY[ph * g.gh + iy] : axis_entry(g.start_h, g.bin_h, ph, iy, g.gh, H, 1);
+    if (kSkip && ty.l == 0.f && ty.h == 0.f) continue;
+    const size_t r0 = static_cast<size_t>(ty.lo) * W, r1 = static_cast<size_t>(ty.hi) * W;
+    for (int ix = 0; ix < g.gw; ++ix) {
+      const Tap tx = use_tab ? tabX[pw * g.gw + ix] : axis_entry(g.start_w, g.bin_w, pw, ix, g.gw, W, 1);
+      if (kSkip && tx.l == 0.f && tx.h == 0.f) continue;
+      const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
+      float v1[V], v2[V], v3[V], v4[V];
+      nv_load<V>(v1, base + (r0 + tx.lo) * C);
+      nv_load<V>(v2, base + (r0 + tx.hi) * C);
+      nv_load<V>(v3, base + (r1 + tx.lo) * C);
+      nv_load<V>(v4, base + (r1 + tx.hi) * C);
+#pragma unroll
+      for (int j = 0; j < V; ++j) acc[j] += w1 * v1[j] + w2 * v2[j] + w3 * v3[j] + w4 * v4[j];
+    }
+  }
+}
+
+constexpr int kNfTabWaves = (2 * kNfTab + kWave - 1) / kWave;   // waves that hold a table entry
+
 template <int V, bool kOutNhwc, int kNfBlock>
 __global__ void __launch_bounds__(kNfBlock)
 roi_align_fwd_nhwc_kernel(Levels L, const float* __restrict__ rois, const int32_t* __restrict__ levels_in,
@@ -67,7 +98,9 @@ roi_align_fwd_nhwc_kernel(Levels L, const float* __restrict__ rois, const int32_
   DETOPS_DYNAMIC_LDS(float, tile);       // kOutNhwc == false: the workgroup's [channels][bins of the group] output block
   __shared__ Tap tabY[kNfTab];
   __shared__ Tap tabX[kNfTab];
+  __shared__ int s_outside[kNfTabWaves];
   constexpr int kNfWaves = kNfBlock / kWave;
+  static_assert(kNfBlock >= 2 * kNfTab, "the tables are built in one pass");
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int bins = PH * PW;
   const int per_roi = groups * cchunks;
@@ -88,12 +121,25 @@ roi_align_fwd_nhwc_kernel(Levels L, const float* __restrict__ rois, const int32_
   const RoiGeom g = roi_geometry(roi, scale, PH, PW, sr);
   const int ny = PH * g.gh, nx = PW * g.gw;
   const bool use_tab = (ny <= kNfTab) && (nx <= kNfTab);
+  // `outside`: some sample of the ROI lies outside the map (the workgroup then takes the summation that skips such samples,
+  // nf_bin_sum).  The first kNfTabWaves waves build the tables in one pass; each leaves its verdict in its own word.
+  bool outside = true;
   if (use_tab) {
+    bool bad = false;
     for (int t = tid; t < ny + nx; t += kNfBlock) {
-      if (t < ny) tabY[t] = axis_entry(g.start_h, g.bin_h, t / g.gh, t % g.gh, g.gh, H, 1);
-      else { const int u = t - ny; tabX[u] = axis_entry(g.start_w, g.bin_w, u / g.gw, u % g.gw, g.gw, W, 1); }
+      Tap e;
+      if (t < ny) tabY[t] = e = axis_entry(g.start_h, g.bin_h, t / g.gh, t % g.gh, g.gh, H, 1);
+      else { const int u = t - ny; tabX[u] = e = axis_entry(g.start_w, g.bin_w, u / g.gw, u % g.gw, g.gw, W, 1); }
+      bad = bad || (e.l == 0.f && e.h == 0.f);
+    }
+    if (wave < kNfTabWaves) {
+      const bool any = __ballot(bad) != 0ull;
+      if (lane == 0) s_outside[wave] = any ? 1 : 0;
     }
     __syncthreads();
+    outside = false;
+#pragma unroll
+    for (int i = 0; i < kNfTabWaves; ++i) outside = outside || s_outside[i] != 0;
   }
 
   const int c0 = chunk * (kWave * V);
@@ -111,21 +157,14 @@ roi_align_fwd_nhwc_kernel(Levels L, const float* __restrict__ rois, const int32_
     float acc[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) acc[j] = 0.f;
-    for (int iy = 0; iy < g.gh; ++iy) {
-      const Tap ty = use_tab ? tabY[ph * g.gh + iy] : axis_entry(g.start_h, g.bin_h, ph, iy, g.gh, H, 1);
-      const size_t r0 = static_cast<size_t>(ty.lo) * W, r1 = static_cast<size_t>(ty.hi) * W;
-      for (int ix = 0; ix < g.gw; ++ix) {
-        const Tap tx = use_tab ? tabX[pw * g.gw + ix] : axis_entry(g.start_w, g.bin_w, pw, ix, g.gw, W, 1);
-        const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
-        float v1[V], v2[V], v3[V], v4[V];
-        nv_load<V>(v1, base + (r0 + tx.lo) * C);
-        nv_load<V>(v2, base + (r0 + tx.hi) * C);
-        nv_load<V>(v3, base + (r1 + tx.lo) * C);
-        nv_load<V>(v4, base + (r1 + tx.hi) * C);
-#pragma unroll
-        for (int j = 0; j < V; ++j) acc[j] += w1 * v1[j] + w2 * v2[j] + w3 * v3[j] + w4 * v4[j];
-      }
-    }
+    // within a bin the sample coordinate grows with the sample index: a bin has a sample outside the map exactly when the
+    // first or the last one of an axis is (only the border bins of a ROI that crosses the border by more than a pixel)
+    bool skip = outside;
+    if (outside && use_tab)
+      skip = nf_outside(tabY[ph * g.gh]) || nf_outside(tabY[ph * g.gh + g.gh - 1]) || nf_outside(tabX[pw * g.gw]) ||
+             nf_outside(tabX[pw * g.gw + g.gw - 1]);
+    if (skip) nf_bin_sum<V, true>(acc, tabY, tabX, use_tab, g, ph, pw, H, W, C, base);
+    else nf_bin_sum<V, false>(acc, tabY, tabX, use_tab, g, ph, pw, H, W, C, base);
 #pragma unroll
     for (int j = 0; j < V; ++j) acc[j] = acc[j] / g.count;
     if (kOutNhwc) {

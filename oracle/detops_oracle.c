@@ -61,6 +61,7 @@ static void pre_calc_bilinear(int height, int width, int pooled_height, int pool
           /* :47-61 out of the map: contributes zero */
           if (y < -1.0 || y > height || x < -1.0 || x > width) {
             memset(&pc, 0, sizeof(pc));
+            pc.pos1 = -1; /* skipped below: see the summation */
             pre_calc[idx++] = pc;
             continue;
           }
@@ -136,6 +137,13 @@ ORACLE_API void oracle_roi_align_forward_f32(const float* bottom_data, const flo
           for (int iy = 0; iy < roi_bin_grid_h; iy++) {
             for (int ix = 0; ix < roi_bin_grid_w; ix++) {
               precalc_t pc = pre_calc[pci];
+              /* A sample out of the map adds 0.  The CPU kernel does it as 0 * data[0] (:196-199), the CUDA kernel returns
+               * before it reads (cuda/ROIAlign_cuda.cu:22-25): the same bits on a finite map (the sum starts at +0.f), and
+               * the CUDA answer — the operator the device library replaces — where pixel 0 holds Inf or NaN. */
+              if (pc.pos1 < 0) {
+                pci++;
+                continue;
+              }
               output_val += pc.w1 * offset_bottom_data[pc.pos1] +
                             pc.w2 * offset_bottom_data[pc.pos2] +
                             pc.w3 * offset_bottom_data[pc.pos3] +

@@ -47,7 +47,15 @@ def roi_align_torch(x, rois, scale, PH, PW, sampling_ratio):
         Ax.scatter_add_(1, xh[:, None], wxh[:, None])
         Ay = Ay.view(PH, gh, H).sum(1)
         Ax = Ax.view(PW, gw, W).sum(1)
-        outs.append(torch.einsum("ph,chw,qw->cpq", Ay, x[b], Ax) / (gh * gw))
+        if bool(torch.isfinite(x[b]).all()):
+            outs.append(torch.einsum("ph,chw,qw->cpq", Ay, x[b], Ax) / (gh * gw))
+            continue
+        # a non-finite plane: a sample outside [-1, size] counts as 0 WITHOUT reading anything (the operator returns before
+        # it touches the map), and a pixel no sample of a bin touches is not read for that bin — so a zero entry of Ay / Ax
+        # must contribute 0, not 0 * Inf
+        rows = torch.where((Ay != 0)[None, :, :, None], Ay[None, :, :, None] * x[b][:, None, :, :], x.new_zeros(())).sum(2)
+        outs.append(torch.where((Ax != 0)[None, None, :, :], Ax[None, None, :, :] * rows[:, :, None, :],
+                                x.new_zeros(())).sum(3) / (gh * gw))
     if not outs:
         return x.new_zeros((0, C, PH, PW))
     return torch.stack(outs)
@@ -78,9 +86,13 @@ def roi_pool_py(inp, rois, scale, PH, PW):
                 if he <= hs or we <= ws:
                     continue
                 win = inp[b, :, hs:he, ws:we].reshape(C, -1)
-                j = win.argmax(1)  # first maximum in row-major order
-                out[k, :, ph, pw] = win[np.arange(C), j]
-                amax[k, :, ph, pw] = (hs + j // (we - ws)) * W + ws + j % (we - ws)
+                # the maximum starts at -FLT_MAX and only a greater value replaces it: a NaN, -inf or -FLT_MAX never does
+                with np.errstate(invalid="ignore"):
+                    cand = np.where(win > np.float32(-np.finfo(np.float32).max), win, -np.inf)
+                j = cand.argmax(1)  # first maximum in row-major order
+                none = np.isneginf(cand[np.arange(C), j])
+                out[k, :, ph, pw] = np.where(none, np.float32(-np.finfo(np.float32).max), win[np.arange(C), j])
+                amax[k, :, ph, pw] = np.where(none, -1, (hs + j // (we - ws)) * W + ws + j % (we - ws))
     return out, amax
 
 
@@ -145,8 +157,11 @@ def deform_psroi_pool_torch(data, rois, trans, no_trans, scale, output_dim, grou
     ncls = 1 if no_trans else trans.shape[1] // 2
     cec = output_dim if no_trans else output_dim // ncls
     ar = torch.arange(P, dtype=dt)
-    part = torch.floor(ar / P * part_size).long()
-    grp = torch.floor(ar * group_size / P).long().clamp(0, group_size - 1)
+    # the cell and group of a bin are integer decisions the operator takes in fp32 (its scalar type): 7 / 23 * 23 is
+    # 6.9999995 there and floors to 6, whatever a wider type would say
+    ar32 = torch.arange(P, dtype=torch.float32)
+    part = torch.floor(ar32 / P * part_size).long()
+    grp = torch.floor(ar32 * group_size / P).long().clamp(0, group_size - 1)
     sub = torch.arange(S, dtype=dt)
     cls_of = torch.arange(output_dim) // cec
     # position-sensitive plane of (ctop, ph, pw)
