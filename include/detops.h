@@ -772,6 +772,45 @@ int detops_image_batch_u8(const uint8_t* raw, int64_t raw_bytes, const int64_t* 
                           float* out, detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Merge of test-time box augmentation (csrc/bbox_aug.hip; the reference's engine/bbox_aug.py maps every pass's BoxList
+ * back with BoxList.transpose / resize, concatenates them per image and runs filter_results' per-class loop).  The passes
+ * of a batch hand in their unfiltered per-class boxes; the merge maps them to the frame of the image's first pass and
+ * compacts the pairs above the score threshold into one NMS segment per (image, class).
+ *
+ *   boxes [R, 4C] fp32, scores [R, C] fp32: the rows of every (image, pass) group, image-major, the T passes of an image in
+ *   order; group g = image * T + pass holds rows row_offset[g] .. row_offset[g + 1] (int32 [N*T + 1] on the device, and the
+ *   same values on the host as row_offset_host: the entry points validate them and size the grid without a device read).
+ *   group_geom int32 [N*T, 3]: the group's frame (w, h) and its flip bit;  group_ratio fp32 [N*T, 2]: float(w0) / float(w),
+ *   float(h0) / float(h) rounded to fp32, (w0, h0) the frame of the image's first pass.
+ * Per box, in fp32, nothing contracted:
+ *     x1, x2 clamped to [0, w - 1], y1, y2 to [0, h - 1]                      (clip_to_image; a NaN stays a NaN)
+ *     flip bit:  x1' = (w - x2) - 1,  x2' = (w - x1) - 1                      (BoxList.transpose(FLIP_LEFT_RIGHT))
+ *     pass > 0:  x * ratio_w, y * ratio_h, one multiply per coordinate        (BoxList.resize; the first pass is not scaled)
+ * (row, class j >= 1) is a candidate when scores[row, j] > score_thresh.  Segment s = image * (C - 1) + (j - 1) holds the
+ * candidates of class j of the image in row order, which is pass order, then row order.
+ *
+ * detops_bbox_aug_merge_count writes seg_offsets int32 [N*(C-1) + 1] (exclusive prefix of the segment lengths) and
+ * totals int32 [2] = {M, the longest segment}; the caller reads totals once, allocates cand_boxes [M, 4] and cand_scores [M]
+ * and calls detops_bbox_aug_merge_write with the SAME inputs, seg_offsets and workspace (capacity = the rows allocated: a
+ * position beyond it is not written).  The order comes from prefix sums (wave ballots, a fixed scan), never from atomics:
+ * two runs write identical bytes.  Every output element is written exactly once; the workspace needs no initialisation.
+ * R == 0, M == 0, N == 0, C == 1 and empty groups are served (seg_offsets all zero where nothing passes).
+ * boxes and cand_boxes are read and written one box per 16-byte access: BOTH MUST BE 16-BYTE ALIGNED (DETOPS_EINVAL if not).
+ * DETOPS_EINVAL: negative sizes, T < 1, N > 65535, R * C >= 2^31, a null pointer that is needed, a row_offset_host that does
+ * not start at 0, end at R or decreases.  A device row_offset that differs from its host copy cannot make the kernels leave
+ * their buffers.
+ * ---------------------------------------------------------------------------------------- */
+size_t detops_bbox_aug_merge_workspace_bytes(int N, int C, int max_image_rows);
+int detops_bbox_aug_merge_count(const float* scores, const int32_t* row_offset, const int32_t* row_offset_host, int R, int C,
+                                int N, int T, float score_thresh, int32_t* seg_offsets, int32_t* totals, void* workspace,
+                                size_t workspace_bytes, detops_stream_t stream);
+int detops_bbox_aug_merge_write(const float* boxes, const float* scores, const int32_t* row_offset,
+                                const int32_t* row_offset_host, const int32_t* group_geom, const float* group_ratio, int R,
+                                int C, int N, int T, float score_thresh, const int32_t* seg_offsets, int64_t capacity,
+                                float* cand_boxes, float* cand_scores, const void* workspace, size_t workspace_bytes,
+                                detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused FrozenBatchNorm2d affine (+ residual) (+ ReLU) — the elementwise tail of every backbone
  * convolution: layers/batch_norm.py:19-31 (`x * scale + bias`), then `F.relu_`, and in the
  * bottleneck tail `out += identity; relu` (modeling/backbone/resnet.py:343-366).

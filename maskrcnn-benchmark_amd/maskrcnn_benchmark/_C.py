@@ -968,6 +968,59 @@ def image_batch(raw, offsets, geom, table, bgr, Hp, Wp, channels_last=False, geo
     return out
 
 
+# ------------------------------------------------------------------------------------------ test-time box augmentation
+def bbox_aug_merge(boxes, scores, row_offset, group_geom, group_ratio, N, T, score_thresh):
+    """The merge of test-time box augmentation (extension; include/detops.h: detops_bbox_aug_merge_count / _write): boxes
+    [R, 4C] and scores [R, C] fp32 are the unfiltered rows of every (image, pass) group, image-major; row_offset int32
+    [N*T + 1], group_geom int32 [N*T, 3] (frame w, h, flip bit) and group_ratio float32 [N*T, 2] are CPU tensors
+    (_bbox_aug_torch.group_records makes the last two).  -> (cand_boxes [M, 4] in the frame of each image's first pass,
+    cand_scores [M], seg_offsets int32 [N*(C-1) + 1] on the device, the longest segment): one NMS segment per (image,
+    class >= 1), pass order then row order inside it.  One host read (M and the longest segment).  CPU tensors take the
+    torch formulation of the same definition (_bbox_aug_torch.py)."""
+    from . import _bbox_aug_torch
+
+    N, T = int(N), int(T)
+    if boxes.dim() != 2 or scores.dim() != 2 or boxes.shape[0] != scores.shape[0] or boxes.shape[1] != 4 * scores.shape[1] \
+            or N < 0 or T < 1 or row_offset.dtype != torch.int32 or row_offset.numel() != N * T + 1 \
+            or group_geom.dtype != torch.int32 or tuple(group_geom.shape) != (N * T, 3) \
+            or group_ratio.dtype != torch.float32 or tuple(group_ratio.shape) != (N * T, 2) \
+            or row_offset.is_cuda or group_geom.is_cuda or group_ratio.is_cuda:
+        raise ValueError("bbox_aug_merge: expected boxes [R, 4C], scores [R, C] and the CPU records row_offset [N*T + 1] int32, "
+                         "group_geom [N*T, 3] int32, group_ratio [N*T, 2] float32")
+    boxes = _f32c("bbox_aug_merge", boxes)
+    scores = _f32c("bbox_aug_merge", scores)
+    if not on_device(boxes) and not on_device(scores):
+        return _bbox_aug_torch.bbox_aug_merge(boxes, scores, row_offset, group_geom, group_ratio, N, T, float(score_thresh))
+    _need_cuda("bbox_aug_merge", boxes, scores)
+    if boxes.data_ptr() % 16:                         # the kernel reads a box as one 16-byte load: a view at an odd offset is copied
+        boxes = boxes.clone()
+    dev = scores.device
+    R, C = scores.shape
+    row_offset = row_offset.contiguous()
+    per_image = row_offset[::T]
+    longest_image = int((per_image[1:] - per_image[:-1]).max()) if N else 0
+    d_off = row_offset.to(dev, non_blocking=True)
+    d_geom = group_geom.contiguous().to(dev, non_blocking=True)
+    d_ratio = group_ratio.contiguous().to(dev, non_blocking=True)
+    seg_offsets = torch.empty((N * max(C - 1, 0) + 1,), dtype=torch.int32, device=dev)
+    totals = torch.empty((2,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.detops_bbox_aug_merge_workspace_bytes(N, C, max(longest_image, 0)))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with _on_device(scores):
+        with _timed(("bbox_aug_merge_count[R=%d,C=%d]", (R, C)), scores):
+            check(lib.detops_bbox_aug_merge_count(ptr(scores), ptr(d_off), ptr(row_offset), R, C, N, T, float(score_thresh),
+                                                  ptr(seg_offsets), ptr(totals), ptr(ws), nbytes, stream_of(scores)),
+                  "bbox_aug_merge_count")
+        M, longest = totals.tolist()                  # the variable-length result forces one readback
+        cand_boxes = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        cand_scores = torch.empty((M,), dtype=torch.float32, device=dev)
+        with _timed(("bbox_aug_merge_write[R=%d,C=%d]", (R, C)), scores):
+            check(lib.detops_bbox_aug_merge_write(ptr(boxes), ptr(scores), ptr(d_off), ptr(row_offset), ptr(d_geom), ptr(d_ratio),
+                                                  R, C, N, T, float(score_thresh), ptr(seg_offsets), M, ptr(cand_boxes),
+                                                  ptr(cand_scores), ptr(ws), nbytes, stream_of(scores)), "bbox_aug_merge_write")
+    return cand_boxes, cand_scores, seg_offsets, longest
+
+
 # ------------------------------------------------------------------------------------------ detection evaluation
 EVAL_COCO_SEGM, EVAL_COCO_BBOX, EVAL_VOC = 0, 1, 2
 EVAL_MAX_GT = _eval_cpu.MAX_GT        # DETOPS_EVAL_MAX_GT: the largest G_p detops_eval_match serves

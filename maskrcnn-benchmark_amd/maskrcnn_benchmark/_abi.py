@@ -76,6 +76,9 @@ SIGNATURES = {
     "detops_polygon_mask_targets": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
     "detops_polygons_to_masks": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P]),
     "detops_image_batch_u8": (c_int, [_P, ctypes.c_int64, _P, _P, _P, c_int, _P] + [c_int] * 4 + [_P, _P]),
+    "detops_bbox_aug_merge_workspace_bytes": (c_size_t, [c_int] * 3),
+    "detops_bbox_aug_merge_count": (c_int, [_P, _P, _P] + [c_int] * 4 + [c_float, _P, _P, _P, c_size_t, _P]),
+    "detops_bbox_aug_merge_write": (c_int, [_P] * 6 + [c_int] * 4 + [c_float, _P, ctypes.c_int64, _P, _P, _P, c_size_t, _P]),
     "detops_mask_pack": (c_int, [_P, _P, _P, c_int, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "detops_mask_pair_counts": (c_int, [_P] * 11 + [c_int, ctypes.c_int64, _P, _P]),
     "detops_eval_iou": (c_int, [c_int] + [_P] * 9 + [c_int, ctypes.c_int64, _P, _P]),

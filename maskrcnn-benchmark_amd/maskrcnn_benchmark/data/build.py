@@ -87,8 +87,14 @@ def make_batch_data_sampler(dataset, sampler, aspect_grouping, images_per_batch,
     return batch_sampler
 
 
-def make_collator(cfg):
-    if collate_batch.device_prep(cfg):
+def deferred_prep(cfg, is_train):
+    """are the pixels of this loader's batches deferred (ToRaw transforms, RawBatchCollator)?  The input path's switch
+    (collate_batch.device_prep), and always under test-time box augmentation: every pass is prepared from the raw bytes."""
+    return collate_batch.device_prep(cfg) or (not is_train and cfg.TEST.BBOX_AUG.ENABLED)
+
+
+def make_collator(cfg, is_train=True):
+    if deferred_prep(cfg, is_train):
         from maskrcnn_benchmark.engine.bench_step import choose_layout
 
         return collate_batch.RawBatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY, cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD,
@@ -104,6 +110,10 @@ def make_data_loader(cfg, is_train=True, is_distributed=False, start_iter=0, ima
     one per name asks for each by name.)"""
     names = cfg.DATASETS.TRAIN if is_train else cfg.DATASETS.TEST
     if _is_synthetic(names):
+        if not is_train and cfg.TEST.BBOX_AUG.ENABLED:
+            raise ValueError("TEST.BBOX_AUG prepares every pass from the raw uint8 images (the deferred input path); the "
+                             "synthetic generator %s makes float tensors: name a COCO-json dataset in DATASETS.TEST"
+                             % (tuple(names),))
         return synthetic.make_data_loader(cfg, is_train=is_train, is_distributed=is_distributed, start_iter=start_iter,
                                           images_per_gpu=images_per_gpu, length=length)
     if not is_train:
@@ -122,13 +132,14 @@ def make_data_loader(cfg, is_train=True, is_distributed=False, start_iter=0, ima
     if not is_train:
         start_iter = 0
     aspect_grouping = [1] if cfg.DATALOADER.ASPECT_RATIO_GROUPING else []
-    transforms = build_transforms(cfg, is_train, device_prep=collate_batch.device_prep(cfg))
+    deferred = deferred_prep(cfg, is_train)
+    transforms = build_transforms(cfg, is_train, device_prep=deferred)
     loaders = []
     for dataset in build_dataset(names, transforms, DatasetCatalog, is_train):
         sampler = make_data_sampler(dataset, shuffle, is_distributed)
         batch_sampler = make_batch_data_sampler(dataset, sampler, aspect_grouping, images_per_gpu, num_iters, start_iter)
         loaders.append(torch.utils.data.DataLoader(dataset, num_workers=cfg.DATALOADER.NUM_WORKERS, batch_sampler=batch_sampler,
-                                                   collate_fn=make_collator(cfg),
-                                                   pin_memory=cfg.MODEL.DEVICE != "cpu" and collate_batch.device_prep(cfg)))
+                                                   collate_fn=make_collator(cfg, is_train),
+                                                   pin_memory=cfg.MODEL.DEVICE != "cpu" and deferred))
     assert len(loaders) == 1
     return loaders[0]

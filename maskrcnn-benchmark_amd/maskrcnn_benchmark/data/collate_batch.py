@@ -28,10 +28,14 @@ class RawImageBatch(object):
     """buffer [bytes] uint8 = offsets int64 [N] | geom int32 [N, 5] | table float32 [3, 256] | padding to 16 | the images'
     RGB HWC bytes back to back.  The offsets count from the start of the buffer."""
 
-    def __init__(self, buffer, geom, bgr, size, channels_last=False):
+    def __init__(self, buffer, geom, bgr, size, channels_last=False, size_divisible=0):
         self.buffer, self.geom, self.bgr = buffer, geom, bool(bgr)        # geom: the records once more, for the host
         self.size, self.channels_last = size, channels_last              # size: (Hp, Wp)
+        self.size_divisible = int(size_divisible)
         self.image_sizes = [(int(g[2]), int(g[3])) for g in geom.tolist()]
+
+    def __len__(self):
+        return self.geom.shape[0]
 
     @staticmethod
     def pack(images, table, bgr, size_divisible=0, channels_last=False):
@@ -49,29 +53,69 @@ class RawImageBatch(object):
         buf[N * 28 + 3072:head] = 0
         for o, n, im in zip(offsets, sizes, images):
             buf[o:o + n] = np.ascontiguousarray(im.data, dtype=np.uint8).reshape(-1)
-        Hp, Wp = (int(geom[:, 2].max()), int(geom[:, 3].max())) if N else (0, 0)
+        geom = torch.from_numpy(geom)
+        return RawImageBatch(torch.from_numpy(buf), geom, bgr, RawImageBatch._padded(geom, size_divisible), channels_last,
+                             size_divisible)
+
+    @staticmethod
+    def _padded(geom, size_divisible):
+        """(Hp, Wp) of the batch tensor: the largest destination, rounded up to size_divisible"""
+        Hp, Wp = (int(geom[:, 2].max()), int(geom[:, 3].max())) if geom.shape[0] else (0, 0)
         if size_divisible > 0:
             d = int(size_divisible)
             Hp, Wp = (Hp + d - 1) // d * d, (Wp + d - 1) // d * d
-        return RawImageBatch(torch.from_numpy(buf), torch.from_numpy(geom), bgr, (Hp, Wp), channels_last)
+        return Hp, Wp
 
     def pin_memory(self):
         """torch's DataLoader(pin_memory=True) calls this in the main process"""
         self.buffer = self.buffer.pin_memory()
         return self
 
-    def to(self, device, *args, **kwargs):
+    def _batch(self, buf, geom, geom_host, size):
         from maskrcnn_benchmark import _C
 
+        N = geom_host.shape[0]
+        offsets = buf[:N * 8].view(torch.int64)
+        table = buf[N * 28:N * 28 + 3072].view(torch.float32).view(3, 256)
+        out = _C.image_batch(buf, offsets, geom, table, self.bgr, size[0], size[1],
+                             channels_last=self.channels_last and buf.device.type != "cpu", geom_host=geom_host)
+        return ImageList(out, [(int(g[2]), int(g[3])) for g in geom_host.tolist()])
+
+    def to(self, device, *args, **kwargs):
         device = torch.device(device)
         N = self.geom.shape[0]
         buf = self.buffer if device.type == "cpu" else self.buffer.to(device, non_blocking=True)
-        offsets = buf[:N * 8].view(torch.int64)
-        geom = buf[N * 8:N * 28].view(torch.int32).view(N, 5)
-        table = buf[N * 28:N * 28 + 3072].view(torch.float32).view(3, 256)
-        out = _C.image_batch(buf, offsets, geom, table, self.bgr, self.size[0], self.size[1],
-                             channels_last=self.channels_last and device.type != "cpu", geom_host=self.geom)
-        return ImageList(out, self.image_sizes)
+        return self._batch(buf, buf[N * 8:N * 28].view(torch.int32).view(N, 5), self.geom, self.size)
+
+    def on(self, device):
+        """The same batch with its bytes on `device`: the ONE host-to-device copy of a batch that is prepared several times
+        (`prepare`).  The host records stay on the host."""
+        device = torch.device(device)
+        here = self.buffer.device
+        if device.type == "cpu" or (here.type == device.type and device.index in (None, here.index)):
+            return self                                # already there ("cuda" names the device the bytes are on)
+        return RawImageBatch(self.buffer.to(device, non_blocking=True), self.geom, self.bgr, self.size, self.channels_last,
+                             self.size_divisible)
+
+    def target(self, min_size, max_size, flip=False):
+        """The records of this batch prepared at another target: every SOURCE image through Resize(min_size, max_size) and,
+        with `flip`, mirrored horizontally -> geom int32 [N, 5] on the host (the batch's own flips are not carried over)."""
+        from .transforms import Resize
+
+        resize = Resize(min_size, max_size)
+        geom = self.geom.clone()
+        for i, (h, w) in enumerate(self.geom[:, :2].tolist()):
+            oh, ow = resize.get_size((w, h))
+            geom[i, 2], geom[i, 3], geom[i, 4] = oh, ow, int(bool(flip))
+        return geom
+
+    def prepare(self, min_size, max_size, flip=False):
+        """-> ImageList of the batch at that target, on the device the bytes are on (`on`): one small record upload and one
+        image_batch launch; the raw bytes are not copied again."""
+        geom = self.target(min_size, max_size, flip)
+        dev = self.buffer.device
+        return self._batch(self.buffer, geom if dev.type == "cpu" else geom.to(dev, non_blocking=True), geom,
+                           self._padded(geom, self.size_divisible))
 
 
 class RawBatchCollator(object):

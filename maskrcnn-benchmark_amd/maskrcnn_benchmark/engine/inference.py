@@ -12,15 +12,51 @@ from maskrcnn_benchmark.data.datasets.evaluation import COCOStyleEvaluator, chec
 from maskrcnn_benchmark.utils.comm import get_world_size
 
 
-def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, bbox_aug=False, device="cuda",
-              expected_results=(), expected_results_sigma_tol=4, output_folder=None):
+def _built_with(model):
+    """the config a detector was built from: the copy its ROI heads keep (a wrapper's `.module` is looked through); None
+    for a model without ROI heads"""
+    for _ in range(4):
+        heads = getattr(model, "roi_heads", None)
+        if heads is not None:
+            return getattr(heads, "cfg", None)
+        model = getattr(model, "module", None)
+        if model is None:
+            break
+    return None
+
+
+def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, bbox_aug=None, device="cuda",
+              expected_results=(), expected_results_sigma_tol=4, output_folder=None, cfg=None):
+    """bbox_aug: test-time box augmentation (engine/bbox_aug.py) with the passes of `cfg.TEST.BBOX_AUG`; model and loader
+    were built from that `cfg` (the reference reads its global cfg there; left out, it is the copy the ROI heads keep).
+    None, the default and what tools/test_net.py gets: as the model was built, i.e. TEST.BBOX_AUG.ENABLED of its config.
+    An explicit value that contradicts the model is an error, not a choice: a model built with BBOX_AUG hands back unfiltered
+    per-class boxes and one built without it hands back detections.  Under box augmentation only the bbox table is made,
+    which is logged."""
     if get_world_size() > 1:
         raise NotImplementedError("evaluation is single-process only: run tools/test_net.py without a distributed launcher "
                                   "(world size %d)" % get_world_size())
-    if bbox_aug:
-        raise NotImplementedError("test-time box augmentation (bbox_aug) is not built")
-    device = torch.device(device)
     logger = logging.getLogger("maskrcnn_benchmark.inference")
+    built_with = _built_with(model)
+    built_aug = None if built_with is None else bool(built_with.TEST.BBOX_AUG.ENABLED)
+    if bbox_aug is None:
+        bbox_aug = bool(built_aug)
+        if bbox_aug:
+            logger.info("the model was built with TEST.BBOX_AUG.ENABLED: evaluating with test-time box augmentation")
+    elif built_aug is not None and bool(bbox_aug) != built_aug:
+        raise ValueError("inference(bbox_aug=%s), but the model was built with TEST.BBOX_AUG.ENABLED %s: the box head's output "
+                         "(unfiltered per-class boxes or detections) is fixed when the model is built" % (bool(bbox_aug), built_aug))
+    if bbox_aug:
+        from .bbox_aug import im_detect_bbox_aug
+
+        cfg = built_with if cfg is None else cfg
+        if cfg is None:
+            raise ValueError("inference(bbox_aug=True) needs cfg=: the config the model and the loader were built from")
+        if tuple(iou_types) != ("bbox",):
+            logger.info("TEST.BBOX_AUG: the mask and keypoint heads are not run under box augmentation; evaluating bbox only "
+                        "(not %s)", ", ".join(t for t in iou_types if t != "bbox"))
+            iou_types = ("bbox",)
+    device = torch.device(device)
     dataset = data_loader.dataset
     logger.info("Start evaluation on {} dataset({} images).".format(dataset_name, len(dataset)))
     streaming = dataset_style(dataset) == "coco"
@@ -35,7 +71,11 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     for images, targets, image_ids in data_loader:
         with torch.no_grad():
             t0 = time.time()
-            output = model(images.to(device))
+            output = im_detect_bbox_aug(model, images, device, cfg) if bbox_aug else model(images.to(device))
+            if not bbox_aug and not box_only and any(o.has_field("scores") and not o.has_field("labels") for o in output):
+                # a model whose config could not be found (a wrapper without `.module`) and that was built with BBOX_AUG
+                raise ValueError("the model returned boxes without `labels`: it was built with TEST.BBOX_AUG.ENABLED and is "
+                                 "evaluated with inference(bbox_aug=True, cfg=...)")
             if device.type != "cpu":
                 torch.cuda.synchronize()
             model_time += time.time() - t0

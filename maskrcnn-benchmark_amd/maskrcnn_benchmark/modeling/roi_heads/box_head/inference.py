@@ -35,8 +35,21 @@ class PostProcessor(nn.Module):
             decoded = decoded.repeat(1, class_prob.shape[1])
         results = []
         for prob, b, shape in zip(class_prob.split(counts, dim=0), decoded.split(counts, dim=0), image_shapes):
-            results.append(self.filter_results(b, prob, shape))
+            if self.bbox_aug_enabled:  # filtered later, over all passes (engine/bbox_aug.py)
+                results.append(self.prepare_boxlist(b, prob, shape))
+            else:
+                results.append(self.filter_results(b, prob, shape))
         return results
+
+    def prepare_boxlist(self, boxes, scores, image_shape):
+        """boxes [n, 4*C], scores [n, C] of one image -> the reference's unfiltered BoxList (inference.py:82-106): bbox
+        [n*C, 4] clipped to the image, `scores` [n*C]; row i*C + j is proposal i's box for class j."""
+        W, H = image_shape
+        boxes = boxes.reshape(-1, 4)
+        hi = device_constant([W - 1, H - 1, W - 1, H - 1], boxes.dtype, boxes.device)
+        out = BoxList(torch.minimum(boxes.clamp(min=0), hi), image_shape, mode="xyxy")
+        out.add_field("scores", scores.reshape(-1))
+        return out
 
     def filter_results(self, boxes, scores, image_shape):
         """boxes [n, 4*C], scores [n, C] of one image -> BoxList(scores, labels).  The per-class
@@ -81,4 +94,4 @@ class PostProcessor(nn.Module):
 def make_roi_box_post_processor(cfg):
     H = cfg.MODEL.ROI_HEADS
     return PostProcessor(H.SCORE_THRESH, H.NMS, H.DETECTIONS_PER_IMG, BoxCoder(weights=H.BBOX_REG_WEIGHTS),
-                         cfg.MODEL.CLS_AGNOSTIC_BBOX_REG, False)
+                         cfg.MODEL.CLS_AGNOSTIC_BBOX_REG, cfg.TEST.BBOX_AUG.ENABLED)

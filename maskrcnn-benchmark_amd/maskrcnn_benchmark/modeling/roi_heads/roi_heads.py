@@ -17,6 +17,10 @@ class CombinedROIHeads(torch.nn.ModuleDict):
         losses = {}
         x, detections, loss_box = self.box(features, proposals, targets)
         losses.update(loss_box)
+        if not self.training and self.cfg.TEST.BBOX_AUG.ENABLED:
+            # test-time box augmentation: the box head hands back unfiltered per-class boxes (no `labels`); the mask and
+            # keypoint heads are not run on them
+            return x, detections, losses
         if self.cfg.MODEL.MASK_ON:
             mask_features = features
             if self.training and self.cfg.MODEL.ROI_MASK_HEAD.SHARE_BOX_FEATURE_EXTRACTOR:

@@ -700,6 +700,85 @@ def bench_input_prep(C, iters, copy_gbs=None):
     return out
 
 
+def bench_bbox_aug(C, iters, copy_gbs=None):
+    """the merge of test-time box augmentation (csrc/bbox_aug.hip): N = 2 images, T = 6 passes, 1000 rows per group, 81
+    classes, about 1 % of the (row, class) pairs above the score threshold.
+    `merge kernels` row: the four launches (count, prefix, offsets, write) on preallocated outputs, HIP events; bytes = what they read
+    (scores twice, the candidates' boxes once) + the candidates written; frac_of_copy_peak = the bytes READ over the time,
+    against the copy row of the same run.  The other rows are per-call host-clock times around a device synchronise (each has
+    host reads inside): _C.bbox_aug_merge as the engine calls it; merge + one segmented NMS + the per-image limit
+    (engine/bbox_aug.py: merge_detections); the torch formulation of the merge on the same device tensors
+    (_bbox_aug_torch.py); and the formulation there was before: PostProcessor.filter_results on each image's concatenated
+    rows, every (row, class) pair padded to a dummy box, one NMS call per image (it includes NMS and the limit, like the
+    merge + NMS + top-k row)."""
+    from maskrcnn_benchmark import _bbox_aug_torch, _lib
+    from maskrcnn_benchmark.engine.bbox_aug import merge_detections
+    from maskrcnn_benchmark.modeling.roi_heads.box_head.inference import PostProcessor
+    N, T, rows, NC, thresh = 2, 6, 1000, 81, 0.05
+    R = N * T * rows
+    rng = np.random.RandomState(7)
+    frames = [[(1201, 800), (1201, 800), (600, 400), (600, 400), (1500, 1001), (1500, 1001)] for _ in range(N)]
+    flips = [0, 1, 0, 1, 0, 1]
+    group = np.repeat(np.arange(N * T), rows)
+    wh = np.array([frames[g // T][g % T] for g in range(N * T)], np.float64)[group]
+    lo = rng.uniform(-0.05, 0.8, (R, NC, 2))
+    boxes = _t((np.concatenate([lo, lo + rng.uniform(0.02, 0.3, lo.shape)], -1) * np.concatenate([wh, wh], 1)[:, None, :])
+               .reshape(R, 4 * NC).astype(np.float32))
+    scores = _t(np.where(rng.rand(R, NC) < 0.01, rng.uniform(0.06, 1.0, (R, NC)), rng.uniform(0.0, 0.04, (R, NC))).astype(np.float32))
+    row_offset = torch.arange(0, R + 1, rows, dtype=torch.int32)
+    geom, ratio = _bbox_aug_torch.group_records(frames, flips)
+    sizes = [f[0] for f in frames]
+
+    def wall(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e6
+
+    cand_boxes, cand_scores, seg_offsets, longest = C.bbox_aug_merge(boxes, scores, row_offset, geom, ratio, N, T, thresh)
+    M = cand_scores.numel()
+    d_off, d_geom, d_ratio = row_offset.cuda(), geom.cuda(), ratio.cuda()
+    totals = torch.empty((2,), dtype=torch.int32, device="cuda")
+    nbytes = int(_lib.lib.detops_bbox_aug_merge_workspace_bytes(N, NC, T * rows))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
+    ptr, st = _lib.ptr, _lib.stream_of
+
+    def kernels():
+        _lib.check(_lib.lib.detops_bbox_aug_merge_count(ptr(scores), ptr(d_off), ptr(row_offset), R, NC, N, T, thresh, ptr(seg_offsets),
+                                                        ptr(totals), ptr(ws), nbytes, st(scores)), "count")
+        _lib.check(_lib.lib.detops_bbox_aug_merge_write(ptr(boxes), ptr(scores), ptr(d_off), ptr(row_offset), ptr(d_geom), ptr(d_ratio),
+                                                        R, NC, N, T, thresh, ptr(seg_offsets), M, ptr(cand_boxes), ptr(cand_scores),
+                                                        ptr(ws), nbytes, st(scores)), "write")
+
+    read = 2 * R * NC * 4 + M * 16
+    us = dev_time_us(kernels, iters)
+    extra = {"candidates": M, "longest_segment": longest, "bytes_read": read}
+    if copy_gbs:
+        extra["frac_of_copy_peak"] = round(read / us / 1e3 / copy_gbs, 4)
+    out = [_entry("bbox_aug merge kernels (count, prefix, offsets, write) N=2 T=6 1000 rows C=81", us, read + M * 20, extra)]
+    n = max(iters // 2, 10)
+    us = wall(lambda: C.bbox_aug_merge(boxes, scores, row_offset, geom, ratio, N, T, thresh), n)
+    out.append(_entry("bbox_aug _C.bbox_aug_merge (record upload, host read of M, allocation)", us, read + M * 20))
+    us = wall(lambda: merge_detections(boxes, scores, row_offset, geom, ratio, sizes, T, thresh, 0.5, 100), n)
+    out.append(_entry("bbox_aug merge + segmented NMS + top-k (merge_detections)", us, read + M * 20))
+    us = wall(lambda: _bbox_aug_torch.bbox_aug_merge(boxes, scores, row_offset, geom, ratio, N, T, thresh), n)
+    out.append(_entry("bbox_aug torch formulation of the merge, same device tensors", us, read + M * 20))
+    post = PostProcessor(thresh, 0.5, 100)
+    per_image = T * rows
+
+    def padded():
+        return [post.filter_results(boxes[i * per_image:(i + 1) * per_image], scores[i * per_image:(i + 1) * per_image], sizes[i])
+                for i in range(N)]
+
+    us = wall(padded, n)
+    out.append(_entry("bbox_aug padded formulation: filter_results per image on the concatenated rows (NMS + top-k)", us,
+                      R * NC * 20))
+    return out
+
+
 def bench_evaluation(C, iters):
     """detection evaluation (csrc/evaluate.hip): the 100 pasted detections of bench_masker against the 20 instances of
     bench_polygons, one 800 x 1333 image, all in one category (every pair is a problem pair: one problem of 100 x 20).
@@ -852,6 +931,9 @@ def main():
     if not only or "input_prep" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_input_prep(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
+    if not only or "bbox_aug" in only:
+        copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
+        res += bench_bbox_aug(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
     if not only or "frozen_bn" in only:
         res += bench_frozen_bn(C, args.iters)
     if not only or "group_norm" in only:
