@@ -495,6 +495,9 @@ roi_align_bwd_nhwc_kernel(Levels L, NbPlan P, NbWs ws, const float* __restrict__
         const int total4 = cc * bins / 4;
         for (int o = 0; o < total4; o += kWave)
           if (o + lane < total4) glds16(src + 4 * (o + lane), gb + 4 * o);
+        // the fast walk multiplies up to kNbMaxC - 1 floats past a channel's last bin by 0: for the chunk's LAST channel
+        // those lie behind the copied block, in LDS nobody wrote (whatever an earlier kernel left: 0 * NaN is NaN)
+        if (lane < kNbMaxC) gb[cc * bins + lane] = 0.f;
       }
       {
         const int q4 = PP / 4;                                           // float4 pieces per row

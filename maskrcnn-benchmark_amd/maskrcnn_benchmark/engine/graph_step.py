@@ -1,8 +1,9 @@
 """A training iteration replayed from a HIP graph (round 6).
 
-The iteration of this package never reads anything back from the device (fixed-length proposal / target
-tensors, device-side counts), so forward + backward + optimizer can be captured ONCE and replayed: the host then enqueues one
-graph launch instead of ~1,000-1,800 kernel launches.  That pays exactly where the step is HOST-bound — R-101 + deformable
+With the mask head in fixed-slot mode, which GraphedTrainStep forces, the iteration of this package never reads anything back
+from the device (fixed-length proposal / target tensors, device-side counts; the default dynamic-slot
+mode reads the positive counts back once per iteration and cannot be captured), so forward + backward + optimizer can be
+captured ONCE and replayed: the host then enqueues one graph launch instead of ~1,000-1,800 kernel launches.  That pays exactly where the step is HOST-bound — R-101 + deformable
 convolutions under fp16 (BASELINE configs[4]): 36.5 ms eager vs 25.2 ms replayed on a slow-host box, tools/graph_probe.py —
 and nothing where the device is the limit (the fp32 headline step, bf16).  The reference has no counterpart (its trainer loop,
 engine/trainer.py:54-89, launches every kernel from Python and synchronises ~66 times per iteration).

@@ -585,6 +585,78 @@ def test_graphed_train_step_mask_rcnn_signatures_seeds_and_fallback():
     assert _C.nms_repaired_segments(_dev()) == 0
 
 
+@pytest.mark.skipif(not _graph_env_ready(), reason="needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 before the HIP runtime starts")
+def test_graphed_train_step_mask_rcnn_losses_equal_the_eager_iterations(monkeypatch):
+    """Mask R-CNN through GraphedTrainStep against the SAME class with max_graphs = 0, where every iteration takes
+    `_run_eager` (same device-side learning rate and seed word), from the same initial weights and with the same warm-up:
+    replay i of the captured run is iteration warmup + i of the eager run.  This is the test that a replay which returned
+    the first batch's proposals, stale pooled features or a stale keep mask would fail.
+    The host half of a sampler's seed is drawn from the generator per CALL and frozen by a capture (engine/graph_step.py: the
+    device word makes the stream new).  Both runs therefore take the host half from the call's position within its
+    iteration, so that iteration n draws the same streams captured or not.
+    Yardstick, as in test_forced_ddp_hook_world1_nccl_matches_plain_step: eager against eager.  Bit-equal -> the first three
+    replays must equal the eager iterations' loss dictionaries exactly; otherwise the first replay is held to the relative
+    2e-3 of max(1, |loss|) of the RetinaNet test above, with the eager-eager spread printed next to it."""
+    from maskrcnn_benchmark import _C
+    from maskrcnn_benchmark.engine.bench_step import build_training, load_cfg, make_device_batches
+    from maskrcnn_benchmark.engine.graph_step import GraphedTrainStep
+    cfg = load_cfg("e2e_mask_rcnn_R_50_FPN_1x.yaml",
+                   ["MODEL.RPN.PRE_NMS_TOP_N_TRAIN", 300, "MODEL.RPN.FPN_POST_NMS_TOP_N_TRAIN", 300,
+                    "MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE", 64])
+    (images, targets), = make_device_batches(cfg, _dev(), images_per_gpu=1, num_batches=1, height=192, width=256)
+    warmup, replays = 2, 3
+    call = [0]
+
+    def seed_by_position(device):
+        call[0] += 1
+        return (0x9E3779B97F4A7C15 * call[0] + 12345) & 0xFFFFFFFFFFFFFFFF
+
+    iteration = GraphedTrainStep._iteration
+
+    def counted_iteration(self, images, targets):
+        call[0] = 0
+        return iteration(self, images, targets)
+
+    monkeypatch.setattr(_C, "_next_sampler_seed", seed_by_position)
+    monkeypatch.setattr(GraphedTrainStep, "_iteration", counted_iteration)
+    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
+
+    def run(max_graphs, calls):
+        torch.manual_seed(0)
+        model, opt, sched, step = build_training(cfg, _dev())
+        g = GraphedTrainStep(step, warmup=warmup, max_graphs=max_graphs)
+        out = []
+        for _ in range(calls):
+            ld = g(images, targets)
+            out.append({k: float(v.detach()) for k, v in ld.items()})
+        torch.cuda.synchronize()
+        return out, g
+
+    _C.nms_repaired_segments(_dev(), reset=True)
+    eager_a, ga = run(0, warmup + replays)
+    eager_b, gb = run(0, warmup + replays)
+    graphed, g = run(1, replays)
+    assert ga.replays == 0 and ga.eager_steps == warmup + replays and not ga._graphs
+    assert g.replays == replays and g.eager_steps == warmup and len(g._graphs) == 1
+    assert int(g.seed) == int(ga.seed) == warmup + replays
+
+    def spread(a, b):
+        return max(abs(a[k] - b[k]) / max(1.0, abs(a[k])) for k in a)
+
+    noise = [spread(a, b) for a, b in zip(eager_a, eager_b)]
+    diff = [spread(eager_a[warmup + i], graphed[i]) for i in range(replays)]
+    deterministic = eager_a == eager_b
+    print("graphed Mask R-CNN step: eager-eager bit-equal = %s, eager-eager spread per iteration %s, graph-eager difference "
+          "per replay %s" % (deterministic, ["%.3g" % v for v in noise], ["%.3g" % v for v in diff]))
+    assert len({tuple(sorted(d.items())) for d in graphed}) == replays            # the replays differ from one another
+    if deterministic:
+        for i in range(replays):
+            assert graphed[i] == eager_a[warmup + i], (i, graphed[i], eager_a[warmup + i])
+    else:
+        assert diff[0] <= 2e-3, (diff[0], noise[warmup])
+    assert _C.nms_repaired_segments(_dev()) == 0
+
+
 # ------------------------------------------------------------------ mixed precision: one multi-tensor weight cast per step
 @pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
 def test_half_weights_gradients_equal_the_per_layer_autocast_gradients(dtype):

@@ -1359,6 +1359,38 @@ def test_roi_align_fpn_backward_channels_last_matches_the_oracle_and_is_reproduc
 
 
 @pytest.mark.gpu
+def test_roi_align_fpn_backward_channels_last_staged_block_does_not_read_stale_lds(monkeypatch):
+    """The NHWC-native backward stages a hit's [channels of the chunk][7 x 7 bins] gradient block in LDS; its branch-free walk
+    multiplies up to three floats past a channel's last bin by 0, and for the chunk's last channel those lie behind the
+    copied block.  They must not be whatever an earlier kernel left in LDS (0 * NaN is NaN).  A first call with 512 channels
+    and an all-NaN gradient leaves NaN in the staging buffers (the region behind a 32-channel block is inside a 64-channel
+    one); the 32-channel call after it, same LDS layout, must stay finite and meet the oracle.  Small maps: the ring plan
+    declines an underfilled launch, and the switch takes the native kernel in any case."""
+    from maskrcnn_benchmark import _C
+    monkeypatch.setattr(_C, "NHWC_BACKWARD", "native")
+    levels, ph, sr, K = [(32, 40), (16, 20), (8, 10), (4, 5)], 7, 2, 40
+    scales = [1.0 / s for s in synth.FPN_STRIDES[:4]]
+    rng = np.random.RandomState(3)
+    s = np.exp(rng.uniform(np.log(8.0), np.log(300.0), K))
+    cx, cy = rng.uniform(0, 160, K), rng.uniform(0, 128, K)
+    rois = np.stack([rng.randint(0, 2, K), cx - s / 2, cy - s / 2, cx + s / 2, cy + s / 2], 1).astype(np.float32)
+    lvn = synth.level_map(rois)
+    g = rng.randn(K, 32, ph, ph).astype(np.float32)
+    dirty = torch.full((K, 512, ph, ph), float("nan"), device=DEV)
+    for _ in range(2):
+        _C.roi_align_fpn_backward(dirty, _t(rois), _t(lvn), [(2, 512, h, w) for h, w in levels], scales, ph, ph, sr, channels_last=True)
+        got = _C.roi_align_fpn_backward(_t(g), _t(rois), _t(lvn), [(2, 32, h, w) for h, w in levels], scales, ph, ph, sr, channels_last=True)
+        for l, (h, w) in enumerate(levels):
+            sel = np.nonzero(lvn == l)[0]
+            want = (oracle.roi_align_backward(g[sel], rois[sel], scales[l], ph, ph, 2, 32, h, w, sr, acc64=True) if sel.size
+                    else np.zeros((2, 32, h, w), np.float32))
+            a = got[l].contiguous().cpu().numpy()
+            assert np.isfinite(a).all(), "level %d: %d non-finite elements, channels %s" % (
+                l, int((~np.isfinite(a)).sum()), sorted(set(np.argwhere(~np.isfinite(a))[:, 1].tolist())))
+            assert np.abs(a - want).max() <= 1e-4 * max(1.0, np.abs(want).max()), "level %d" % l
+
+
+@pytest.mark.gpu
 def test_roi_align_channels_last_adjoint_identity_at_model_size():
     """<fwd(x), g> == <x, bwd(g)> for the NHWC pair at the model's size (size-independent property; fp64 accumulation of the
     two inner products on the host)"""
