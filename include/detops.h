@@ -604,6 +604,44 @@ int detops_paste_masks_rle_write(const void* masks, int dtype, const float* boxe
                                  int padding, float threshold, int max_w, const int64_t* run_offset, int32_t* counts,
                                  void* workspace, size_t workspace_bytes, detops_stream_t stream);
 
+/* ---- Compressed RLE strings (csrc/rle_string.hip) ------------------------------------------------------------------------
+ * The `counts` string of a COCO results file: a restatement of pycocotools' rleToString, written from knowledge of that
+ * code (pycocotools is not installed where this library is built and tested: nobody has run this against it).
+ * For the runs c[0 .. m) of one mask (int32, column-major, starting with a 0-run, as detops_paste_masks_rle_write and
+ * rle_encode make them):
+ *   - for i in order: x = c[i], and x -= c[i - 2] when i > 2.  GREATER THAN 2: runs 0, 1, 2 are coded as they are;
+ *   - x is a signed 64-bit value;
+ *   - repeat:
+ *       1. ch = x & 0x1f
+ *       2. x >>= 5 (arithmetic shift)
+ *       3. more = (x != -1) if ch & 0x10, else (x != 0)
+ *       4. if more, ch |= 0x20
+ *       5. emit the byte ch + 48
+ *       6. stop when more is false.
+ * The number of bytes of one value is the smallest k >= 1 with -2^(5k-1) <= x < 2^(5k-1); the difference of two int32
+ * values takes at most 7.  (pycocotools itself reserves 6 per run; every int32 input is coded by the rule above, nothing
+ * is refused.)  [16] -> "`0", [0, 5, 3] -> "053", [15, 16, 17, 1] -> "?`0a0A", [1066400] -> "P]aP1".
+ *
+ * detops_rle_string_count / _write — the strings of N masks from their flat run array: counts [total] int32, run_offset
+ *   [N + 1] int64 (run_offset[0] = 0, non-decreasing, run_offset[N] = total; a mask may have no runs: the empty string).
+ *     _count: byte_offset [N + 1] int64 (device) = exclusive sum of the strings' lengths;
+ *     the caller reads byte_offset[N] (the one host read of the path) and allocates out [byte_offset[N]] uint8;
+ *     _write: fills out; mask n's string is out[byte_offset[n] .. byte_offset[n + 1]), no terminator.
+ *   Both calls take the same workspace of detops_rle_string_workspace_bytes(total) bytes, untouched in between: the
+ *   write call places every chunk from what the count call left there and reads nothing else of the count's results;
+ *   byte_offset is in its signature so that the pair reads as count / write of one result, and is only checked for null.
+ *   The work is cut by chunks of the flat run array, not by mask; offsets are prefix sums in a fixed order (no atomics): every
+ *   byte of out is written exactly once, nothing outside it, and two runs give identical bytes.
+ *   Returns: DETOPS_EINVAL for N < 0, total < 0 or a null pointer; DETOPS_EWORKSPACE for a workspace smaller than the
+ *   query's answer.  N == 0 or total == 0 returns 0 with nothing launched and nothing written (the caller's byte_offset
+ *   is then all zeros by its own doing). */
+size_t detops_rle_string_workspace_bytes(int64_t total);
+int detops_rle_string_count(const int32_t* counts, const int64_t* run_offset, int64_t total, int N, int64_t* byte_offset,
+                            void* workspace, size_t workspace_bytes, detops_stream_t stream);
+int detops_rle_string_write(const int32_t* counts, const int64_t* run_offset, int64_t total, int N,
+                            const int64_t* byte_offset, uint8_t* out, const void* workspace, size_t workspace_bytes,
+                            detops_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Polygon instance masks (extensions; the reference rasterises polygons one ROI at a time on the CPU through pycocotools:
  * structures/segmentation_mask.py:273-335, roi_heads/mask_head/loss.py:11-42, "FIXME: CPU computation bottleneck").

@@ -24,7 +24,7 @@ import os
 import numpy as np
 import torch
 
-from . import _eval_cpu, _lib
+from . import _eval_cpu, _lib, _rle_cpu
 from ._lib import check, lib, ptr, stream_of
 
 # ------------------------------------------------------------------------------------------ helpers
@@ -758,6 +758,49 @@ def paste_masks_rle(masks, boxes, sizes, threshold=0.5, padding=1, counts=None):
             check(lib.detops_paste_masks_rle_write(*args, ptr(run_offset), ptr(out), ptr(ws), nbytes, stream_of(masks)),
                   "paste_masks_rle_write")
     return out, run_offset
+
+
+def rle_strings(counts, run_offset):
+    """The compressed strings of COCO result files from uncompressed runs (extension; include/detops.h: "Compressed RLE
+    strings", detops_rle_string_count / _write): counts int32 [total], run_offset int64 [N + 1], as paste_masks_rle makes
+    them -> (bytes uint8 [B], byte_offset int64 [N + 1]) on the inputs' device; mask n's string is
+    bytes[byte_offset[n]:byte_offset[n + 1]].  One host read (the total B) sizes `bytes`.  CPU tensors take the numpy
+    statement of the same definition (_rle_cpu.py)."""
+    if counts.dtype != torch.int32 or run_offset.dtype != torch.int64 or counts.dim() != 1 or run_offset.dim() != 1 \
+            or run_offset.numel() < 1:
+        raise ValueError("rle_strings: expected counts int32 [total] and run_offset int64 [N + 1]")
+    if counts.device != run_offset.device:
+        raise ValueError("rle_strings: counts and run_offset live on different devices")
+    if not counts.is_cuda:
+        data, off = _rle_cpu.rle_strings(counts.numpy(), run_offset.numpy())
+        return torch.from_numpy(data), torch.from_numpy(off)
+    counts, run_offset = counts.contiguous(), run_offset.contiguous()
+    total, N = counts.numel(), run_offset.numel() - 1
+    dev = counts.device
+    byte_offset = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+    if N == 0 or total == 0:
+        return torch.empty((0,), dtype=torch.uint8, device=dev), byte_offset
+    nbytes = int(lib.detops_rle_string_workspace_bytes(total))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with _on_device(counts):
+        with _timed(("rle_string_count[N=%d,runs=%d]", (N, total)), counts):
+            check(lib.detops_rle_string_count(ptr(counts), ptr(run_offset), total, N, ptr(byte_offset), ptr(ws), nbytes,
+                                              stream_of(counts)), "rle_string_count")
+        out = torch.empty((int(byte_offset[-1].item()),), dtype=torch.uint8, device=dev)
+        with _timed(("rle_string_write[N=%d,runs=%d]", (N, total)), counts):
+            check(lib.detops_rle_string_write(ptr(counts), ptr(run_offset), total, N, ptr(byte_offset), ptr(out), ptr(ws),
+                                              nbytes, stream_of(counts)), "rle_string_write")
+    return out, byte_offset
+
+
+def rle_string_list(data, byte_offset):
+    """(bytes, byte_offset) of rle_strings -> a list of N str.  Device tensors cross in ONE copy (the offsets in front of
+    the bytes), then one bytes.decode("ascii") and slices."""
+    n8 = byte_offset.numel() * 8
+    if data.is_cuda:
+        host = torch.cat([byte_offset.contiguous().view(torch.uint8), data]).cpu().numpy()
+        return _rle_cpu.to_str_list(host[n8:], host[:n8].view(np.int64))
+    return _rle_cpu.to_str_list(data.numpy(), byte_offset.numpy())
 
 
 # ------------------------------------------------------------------------------------------ target assignment

@@ -73,6 +73,9 @@ SIGNATURES = {
     "detops_paste_masks_rle_workspace_bytes": (c_size_t, [c_int, c_int]),
     "detops_paste_masks_rle_count": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, c_size_t, _P]),
     "detops_paste_masks_rle_write": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_size_t, _P]),
+    "detops_rle_string_workspace_bytes": (c_size_t, [ctypes.c_int64]),
+    "detops_rle_string_count": (c_int, [_P, _P, ctypes.c_int64, c_int, _P, _P, c_size_t, _P]),
+    "detops_rle_string_write": (c_int, [_P, _P, ctypes.c_int64, c_int, _P, _P, _P, c_size_t, _P]),
     "detops_polygon_mask_targets": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
     "detops_polygons_to_masks": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P]),
     "detops_image_batch_u8": (c_int, [_P, ctypes.c_int64, _P, _P, _P, c_int, _P] + [c_int] * 4 + [_P, _P]),

@@ -1,6 +1,8 @@
 """Inference and evaluation loop (reference engine/inference.py) as a streaming evaluation: per batch, loader ->
 model(images.to(device)) -> targets to the device -> evaluator.update; the predictions are matched against the ground truth
-where they were made and only the match records are kept (data/datasets/evaluation/coco_style.py).  Single process only.
+where they were made and only the match records are kept (data/datasets/evaluation/coco_style.py).  With an output folder the
+detections themselves are written as COCO result files (data/datasets/evaluation/coco_results.py: bbox.json, segm.json,
+keypoints.json), batch by batch next to the evaluator; `evaluate=False` writes them and matches nothing.  Single process only.
 Datasets that are not COCO-shaped keep the reference's flow: the predictions are collected and handed to `evaluate`."""
 import logging
 import os
@@ -8,7 +10,9 @@ import time
 
 import torch
 
-from maskrcnn_benchmark.data.datasets.evaluation import COCOStyleEvaluator, check_scope, dataset_style, evaluate, finish_coco
+from maskrcnn_benchmark.data.datasets.evaluation import COCOStyleEvaluator, check_scope, dataset_style, finish_coco
+from maskrcnn_benchmark.data.datasets.evaluation import evaluate as evaluate_predictions
+from maskrcnn_benchmark.data.datasets.evaluation.coco_results import COCOResultsWriter
 from maskrcnn_benchmark.utils.comm import get_world_size
 
 
@@ -26,13 +30,19 @@ def _built_with(model):
 
 
 def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, bbox_aug=None, device="cuda",
-              expected_results=(), expected_results_sigma_tol=4, output_folder=None, cfg=None):
+              expected_results=(), expected_results_sigma_tol=4, output_folder=None, cfg=None, evaluate=True):
     """bbox_aug: test-time box augmentation (engine/bbox_aug.py) with the passes of `cfg.TEST.BBOX_AUG`; model and loader
     were built from that `cfg` (the reference reads its global cfg there; left out, it is the copy the ROI heads keep).
     None, the default and what tools/test_net.py gets: as the model was built, i.e. TEST.BBOX_AUG.ENABLED of its config.
     An explicit value that contradicts the model is an error, not a choice: a model built with BBOX_AUG hands back unfiltered
     per-class boxes and one built without it hands back detections.  Under box augmentation only the bbox table is made,
-    which is logged."""
+    which is logged.
+    evaluate=False (COCO-shaped datasets, `output_folder` required): results only.  The model runs and the result files of
+    `iou_types` are written; no evaluator is built, the evaluator's scope is not checked ("keypoints" is allowed: OKS is not
+    needed to write keypoints.json) and the targets are neither moved nor matched: the way to run a keypoint model or a test
+    set without annotations.  -> {iou type: path of its file}."""
+    if not evaluate and not output_folder:
+        raise ValueError("inference(evaluate=False) writes result files only: it needs output_folder=")
     if get_world_size() > 1:
         raise NotImplementedError("evaluation is single-process only: run tools/test_net.py without a distributed launcher "
                                   "(world size %d)" % get_world_size())
@@ -60,10 +70,15 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     dataset = data_loader.dataset
     logger.info("Start evaluation on {} dataset({} images).".format(dataset_name, len(dataset)))
     streaming = dataset_style(dataset) == "coco"
-    evaluator = None
-    if streaming:
+    evaluator = writer = None
+    if not evaluate and (not streaming or box_only):
+        raise NotImplementedError("inference(evaluate=False): result files are written for COCO-shaped datasets and detections "
+                                  "only (not box_only proposals)")
+    if streaming and evaluate:
         check_scope(box_only, iou_types)
         evaluator = COCOStyleEvaluator(iou_types, getattr(dataset, "num_classes", None) or 81)
+    if streaming and output_folder and not box_only:
+        writer = COCOResultsWriter(dataset, iou_types)
     model.eval()
     predictions = {}
     start = time.time()
@@ -79,16 +94,25 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
             if device.type != "cpu":
                 torch.cuda.synchronize()
             model_time += time.time() - t0
-            if streaming:
+            if writer is not None:
+                writer.update(output, image_ids)
+            if evaluator is not None:
                 evaluator.update(output, [t.to(device) for t in targets])
-            else:
+            elif not streaming:
                 predictions.update({i: o.to("cpu") for i, o in zip(image_ids, output)})
     total = time.time() - start
     n = max(len(dataset), 1)
-    logger.info("Total run time: {:.1f} s ({:.4f} s / img, matching included)".format(total, total / n))
+    logger.info("Total run time: {:.1f} s ({:.4f} s / img, matching and result files included)".format(total, total / n))
     logger.info("Model inference time: {:.1f} s ({:.4f} s / img)".format(model_time, model_time / n))
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
+    paths = {}
+    if writer is not None:
+        paths = writer.save(output_folder)
+        for t, path in paths.items():
+            logger.info("Wrote {} {} results of {} images to {}".format(len(writer.results[t]), t, writer.num_images, path))
+    if not evaluate:
+        return paths
     if streaming:
         logger.info("Matched {} detections against {} ground truths of {} images".format(
             evaluator.num_detections, evaluator.num_groundtruths, evaluator.num_images))
@@ -96,6 +120,6 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     predictions = [predictions[i] for i in sorted(predictions)]
     if output_folder:
         torch.save(predictions, os.path.join(output_folder, "predictions.pth"))
-    return evaluate(dataset=dataset, predictions=predictions, output_folder=output_folder, box_only=box_only,
-                    iou_types=iou_types, expected_results=expected_results,
-                    expected_results_sigma_tol=expected_results_sigma_tol)
+    return evaluate_predictions(dataset=dataset, predictions=predictions, output_folder=output_folder, box_only=box_only,
+                                iou_types=iou_types, expected_results=expected_results,
+                                expected_results_sigma_tol=expected_results_sigma_tol)

@@ -68,6 +68,14 @@ def rle_encode(plane):
     return {"size": [H, W], "counts": (edges[1:] - edges[:-1]).tolist()}
 
 
+def compress_rles(rles):
+    """a list of uncompressed {"size", "counts": [...]} -> the same masks with `counts` as COCO's compressed strings"""
+    runs = [torch.tensor(r["counts"], dtype=torch.int32) for r in rles]
+    run_offset = torch.tensor([0] + [len(r) for r in runs], dtype=torch.int64).cumsum(0)
+    strings = _C.rle_string_list(*_C.rle_strings(torch.cat(runs) if runs else torch.empty(0, dtype=torch.int32), run_offset))
+    return [{"size": list(r["size"]), "counts": s} for r, s in zip(rles, strings)]
+
+
 class Masker(object):
     """Projects the masks of each image into the image at the locations of its boxes (reference :162-199)"""
 
@@ -139,7 +147,14 @@ class MaskPostProcessor(nn.Module):
 class MaskPostProcessorCOCOFormat(MaskPostProcessor):
     """The pasted masks in COCO format (reference :64-85): field "mask" is a list with one
     {"size": [H, W], "counts": [...]} per detection — UNCOMPRESSED RLE, which pycocotools reads itself (frPyObjects); the
-    reference's compressed strings need pycocotools.  On the device the image-size planes are never stored."""
+    reference's compressed strings need pycocotools.  On the device the image-size planes are never stored.
+    `compressed=True`: {"size": [H, W], "counts": "<str>"} as the reference's field holds, the strings of COCO result files
+    (include/detops.h, "Compressed RLE strings": `_C.rle_strings` behind `_C.paste_masks_rle`; on the device the runs never
+    become Python lists, only the strings' bytes cross)."""
+
+    def __init__(self, masker=None, compressed=False):
+        super(MaskPostProcessorCOCOFormat, self).__init__(masker)
+        self.compressed = compressed
 
     def forward(self, x, boxes):
         if not self.masker:
@@ -152,8 +167,11 @@ class MaskPostProcessorCOCOFormat(MaskPostProcessor):
         if _C.on_device(x) and sum(per_image):
             counts, run_offset = _C.paste_masks_rle(torch.cat(prob), torch.cat([b.bbox for b in xyxy]), sizes, threshold,
                                                     padding, counts=per_image)
-            offs, runs = run_offset.cpu().tolist(), counts.cpu().tolist()
-            flat = [runs[offs[i]:offs[i + 1]] for i in range(sum(per_image))]
+            if self.compressed:
+                flat = _C.rle_string_list(*_C.rle_strings(counts, run_offset))
+            else:
+                offs, runs = run_offset.cpu().tolist(), counts.cpu().tolist()
+                flat = [runs[offs[i]:offs[i + 1]] for i in range(sum(per_image))]
             rles, k = [], 0
             for (h, w), c in zip(sizes, per_image):
                 rles.append([{"size": [h, w], "counts": r} for r in flat[k:k + c]])
@@ -161,6 +179,8 @@ class MaskPostProcessorCOCOFormat(MaskPostProcessor):
         else:
             rles = [[rle_encode(m[0]) for m in paste_masks_torch(p, b.bbox, h, w, threshold, padding).cpu()]
                     for p, b, (h, w) in zip(prob, xyxy, sizes)]
+            if self.compressed:
+                rles = [compress_rles(r) for r in rles]
         results = []
         for r, b in zip(rles, boxes):
             out = b.copy_with_fields(b.fields())

@@ -779,6 +779,89 @@ def bench_bbox_aug(C, iters, copy_gbs=None):
     return out
 
 
+def bench_coco_results(C, iters, copy_gbs=None):
+    """compressed RLE strings of COCO result files (csrc/rle_string.hip): the runs of bench_masker's case, 100 detections of
+    one 800 x 1333 image at M = 28, straight from paste_masks_rle.
+    `kernels` row: the launches of the two calls (count + offsets, write) on preallocated outputs, HIP events; bytes = the counts
+    read by both passes + the strings written; bytes_written / time against the copy row of the same run is
+    frac_of_copy_peak.  The other rows are host-clock times around a device synchronise, per call: _C.rle_strings plus the
+    conversion to a list of str (one host read of the total, one device-to-host copy of offsets and bytes, one decode); the
+    numpy statement (_rle_cpu.py) on the same counts INCLUDING the device-to-host copy of the counts and offsets it needs;
+    and the literal Python loop of the definition on the first 10 detections' runs (already on the host), scaled to all."""
+    from maskrcnn_benchmark import _lib, _rle_cpu
+    g = torch.Generator().manual_seed(5)
+    N, H, W, M = 100, 800, 1333, 28
+    s_ = torch.exp(torch.empty(N, 2).uniform_(np.log(32), np.log(800), generator=g))
+    xy = torch.rand(N, 2, generator=g) * torch.tensor([W - 32.0, H - 32.0])
+    boxes = torch.cat([xy, xy + s_], 1).cuda()
+    maps = torch.sigmoid(3 * torch.randn(N, 1, M, M, generator=g)).cuda()
+    counts, run_offset = C.paste_masks_rle(maps, boxes, [(H, W)], 0.5, 1, counts=[N])
+    total = counts.numel()
+    data, byte_offset = C.rle_strings(counts, run_offset)
+    strings = C.rle_string_list(data, byte_offset)
+    B = data.numel()
+    lib, ptr, st = _lib.lib, _lib.ptr, _lib.stream_of
+    nbytes = int(lib.detops_rle_string_workspace_bytes(total))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
+
+    def kernels():
+        _lib.check(lib.detops_rle_string_count(ptr(counts), ptr(run_offset), total, N, ptr(byte_offset), ptr(ws), nbytes, st(counts)),
+                   "count")
+        _lib.check(lib.detops_rle_string_write(ptr(counts), ptr(run_offset), total, N, ptr(byte_offset), ptr(data), ptr(ws), nbytes,
+                                               st(counts)), "write")
+
+    def wall(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e6
+
+    def numpy_path():
+        d, off = _rle_cpu.rle_strings(counts.cpu().numpy(), run_offset.cpu().numpy())
+        return _rle_cpu.to_str_list(d, off)
+
+    def literal(runs):
+        out = []
+        for i in range(len(runs)):
+            x = runs[i] - runs[i - 2] if i > 2 else runs[i]
+            while True:
+                ch = x & 0x1f
+                x >>= 5
+                more = (x != -1) if ch & 0x10 else (x != 0)
+                if more:
+                    ch |= 0x20
+                out.append(ch + 48)
+                if not more:
+                    break
+        return bytes(out).decode("ascii")
+
+    us = dev_time_us(kernels, iters)
+    extra = {"runs": total, "string_bytes": B}
+    if copy_gbs:
+        extra["frac_of_copy_peak"] = round(B / us / 1e3 / copy_gbs, 6)
+    out = [_entry("coco_results rle_string kernels (count, offsets, write) N=100 800x1333", us, 2 * total * 4 + B, extra)]
+    assert numpy_path() == strings
+    n = max(iters // 2, 10)
+    dev_us = wall(lambda: C.rle_string_list(*C.rle_strings(counts, run_offset)), n)
+    out.append(_entry("coco_results _C.rle_strings + list of str (host read of B, one D2H copy, decode)", dev_us, 2 * total * 4 + 2 * B))
+    np_us = wall(numpy_path, n)
+    out.append(_entry("coco_results numpy path on the same counts (D2H copy of counts and offsets included)", np_us,
+                      2 * total * 4 + B, {"numpy_over_device": round(np_us / dev_us, 2)}))
+    offs = run_offset.cpu().tolist()
+    host_runs = [counts[offs[i]:offs[i + 1]].cpu().tolist() for i in range(10)]
+    assert [literal(r) for r in host_runs] == strings[:10]
+    t0 = time.perf_counter()
+    for r in host_runs:
+        literal(r)
+    lit_us = (time.perf_counter() - t0) * 1e6 * total / max(offs[10], 1)
+    out.append(_entry("coco_results literal Python loop, first 10 detections scaled to %d runs" % total, lit_us, total * 4 + B,
+                      {"runs_timed": offs[10], "literal_over_device": round(lit_us / dev_us, 1)}))
+    return out
+
+
 def bench_evaluation(C, iters):
     """detection evaluation (csrc/evaluate.hip): the 100 pasted detections of bench_masker against the 20 instances of
     bench_polygons, one 800 x 1333 image, all in one category (every pair is a problem pair: one problem of 100 x 20).
@@ -928,6 +1011,9 @@ def main():
         res += bench_polygons(C, args.iters)
     if not only or "evaluation" in only:
         res += bench_evaluation(C, args.iters)
+    if not only or "coco_results" in only:
+        copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
+        res += bench_coco_results(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
     if not only or "input_prep" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_input_prep(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
