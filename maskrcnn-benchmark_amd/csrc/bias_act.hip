@@ -39,8 +39,7 @@ bias_act_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, T* _
     if (kRelu) {
       const VT m = yv[i];
 #pragma unroll
-      for (int j = 0; j < kBaV; ++j)
-        if (Io<T>::ld(m.v[j]) <= 0.f) g.v[j] = Io<T>::st(0.f);   // threshold_backward: passes where y is NaN
+      for (int j = 0; j < kBaV; ++j) g.v[j] = relu_bwd(g.v[j], m.v[j]);
       xo[i] = g;
     } else if (gx != gy) {
       xo[i] = g;
@@ -61,30 +60,9 @@ bias_act_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, T* _
   }
 }
 
-// grad_bias[c] = sum_b partials[b][c]: a workgroup per 32 channels, 32 lanes of partial rows per channel (lane r adds rows
-// r, r + 32, ... in order), then the 32 lane sums in lane order through LDS — a fixed order, and 32x shorter dependent
-// chains than one thread per channel (which took 156 us for 1024 partial rows).
-constexpr int kBfCh = 32, kBfRows = 32;
-__global__ void __launch_bounds__(kBfCh * kBfRows)
-bias_grad_finish_kernel(const float* __restrict__ partials, float* __restrict__ gb, int C, int blocks) {
-  __shared__ float red[kBfRows][kBfCh + 1];
-  const int cl = threadIdx.x % kBfCh, r = threadIdx.x / kBfCh;
-  const int c = static_cast<int>(blockIdx.x) * kBfCh + cl;
-  float s = 0.f;
-  if (c < C)
-    for (int b = r; b < blocks; b += kBfRows) s += partials[static_cast<size_t>(b) * C + c];
-  red[r][cl] = s;
-  __syncthreads();
-  if (r == 0 && c < C) {
-    float t = red[0][cl];
-    for (int q = 1; q < kBfRows; ++q) t += red[q][cl];
-    gb[c] = t;
-  }
-}
-
 // Column sums of a [rows, C] matrix for ANY C <= 256 (the RPN's 3 / 12-channel outputs, the mask logits' 81): a thread is
 // (row lane, channel) with the channel count padded to a power of two, consecutive threads read consecutive addresses;
-// per-workgroup partial sums in row-lane order through LDS, then bias_grad_finish_kernel.
+// per-workgroup partial sums in row-lane order through LDS, then column_partials_finish_kernel (detops_dtype.h).
 template <typename T>
 __global__ void __launch_bounds__(kBaThreads)
 column_sum_kernel(const T* __restrict__ x, float* __restrict__ partials, int C, int Cp, int64_t rows) {
@@ -140,9 +118,7 @@ int bias_act_backward(const void* grad_y, const void* y, void* grad_x, float* gr
     return launch_status();
   });
   if (e) return e;
-  hipLaunchKernelGGL(bias_grad_finish_kernel, dim3(static_cast<unsigned>(ceil_div64(C, kBfCh))), dim3(kBfCh * kBfRows), 0, st, partials,
-                     grad_bias, C, blocks);
-  return launch_status();
+  return column_partials_finish(partials, grad_bias, nullptr, C, blocks, C, 0, st);
 }
 
 }  // namespace
@@ -181,9 +157,7 @@ int column_sum_run(const void* x, float* out, int64_t rows, int C, void* workspa
                      Cp, rows);
   int e = launch_status();
   if (e) return e;
-  hipLaunchKernelGGL(bias_grad_finish_kernel, dim3(static_cast<unsigned>(ceil_div64(C, kBfCh))), dim3(kBfCh * kBfRows), 0, st, partials, out,
-                     C, static_cast<int>(blocks));
-  return launch_status();
+  return column_partials_finish(partials, out, nullptr, C, blocks, C, 0, st);
 }
 }  // namespace
 

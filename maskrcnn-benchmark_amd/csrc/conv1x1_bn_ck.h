@@ -4,7 +4,7 @@
 // taken from CK's own instance lists (the ones MIOpen's tuning database names for these shapes), not re-typed here.
 // Each conv1x1_bn_t*.hip instantiates a part of the (tile, stride, residual) grid so that the build stays parallel.
 #pragma once
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 struct Conv1x1BnArgs {
   const float* x;       // [N, H, W, C]
@@ -40,13 +40,13 @@ int conv1x1_bn_s2(const Conv1x1BnArgs& a, int config, bool check_only);   // str
 namespace conv1x1_bn {
 
 // The epilogue, in the operation order of frozen_bn_fwd_nhwc_kernel (csrc/frozen_bn.hip): product and sum rounded
-// separately (no FMA), then the residual, then torch's ReLU (NaN stays NaN).
+// separately (no FMA), then the residual, then the library's ReLU rule (relu_fwd).
 struct FrozenBnAct {
   template <typename E, typename C, typename S, typename B>
   __host__ __device__ void operator()(E& e, const C& c, const S& s, const B& b) const {
 #pragma clang fp contract(off)
     float t = c * s + b;
-    if (relu) t = t <= 0.f ? 0.f : t;
+    if (relu) t = relu_fwd(t);
     e = t;
   }
   template <typename E, typename C, typename S, typename B, typename R>
@@ -54,7 +54,7 @@ struct FrozenBnAct {
 #pragma clang fp contract(off)
     float t = c * s + b;
     t = t + r;
-    if (relu) t = t <= 0.f ? 0.f : t;
+    if (relu) t = relu_fwd(t);
     e = t;
   }
   int relu;

@@ -1,6 +1,6 @@
 // detops_dtype.h — what the elementwise and loss kernels share: storage-type I/O, 16-byte vectors, the host-side step from
-// a run-time dtype code / vector width / flag to a template argument, and single-value wave reductions.  Only helpers with
-// at least two users live here.
+// a run-time dtype code / vector width / flag to a template argument, the wave and workgroup sums in the library's one
+// fixed order, the finish kernel for column partials, and the fused ReLU rule.  Only helpers with at least two users live here.
 #pragma once
 #include <initializer_list>
 #include <type_traits>
@@ -80,3 +80,82 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ float wave_sum_all(float v) { return __shfl(wave_sum(v), 0); }
 __device__ __forceinline__ float wave_max_all(float v) { return __shfl(wave_max(v), 0); }
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
+  return v;
+}
+
+// ---- THE fixed-order sum of N values over a workgroup of kThreads threads (T = float | int), the library's one order
+// for every loss and count: a thread first adds its own strided share (the caller's loop), then wave_sum's shuffle tree
+// inside each wave, then the waves' values in wave order starting from zero.  Two runs give identical bits.
+// Contract: every thread of the workgroup calls it, in uniform control flow (it holds a barrier).  On return EVERY
+// thread holds the N sums in v.  `scratch` is LDS; other threads may still be reading it on return, so it (this
+// function included) may be written again only after a later __syncthreads().
+template <int kThreads, typename T, int N>
+__device__ __forceinline__ void block_sum(T (&v)[N], T (&scratch)[N][kThreads / kWave]) {
+  static_assert(kThreads % kWave == 0, "whole waves");
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const T w = wave_sum(v[k]);
+    if ((threadIdx.x & (kWave - 1)) == 0) scratch[k][threadIdx.x / kWave] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    T t = 0;
+#pragma unroll
+    for (int j = 0; j < kThreads / kWave; ++j) t += scratch[k][j];
+    v[k] = t;
+  }
+}
+// one value: `scratch` holds kThreads / kWave elements
+template <int kThreads, typename T>
+__device__ __forceinline__ T block_sum(T v, T (&scratch)[kThreads / kWave]) {
+  T a[1] = {v};
+  block_sum<kThreads>(a, reinterpret_cast<T (&)[1][kThreads / kWave]>(scratch));
+  return a[0];
+}
+
+// ---- THE fused ReLU rule, torch's, for every kernel that folds a ReLU into its epilogue or its backward
+// forward: torch.relu(t) — the comparison is false for NaN, so NaN stays NaN (and -0.0 becomes +0.0)
+__host__ __device__ __forceinline__ float relu_fwd(float t) { return t <= 0.f ? 0.f : t; }
+// backward: aten.threshold_backward(g, y, 0) = y <= 0 ? 0 : g — a NaN activation PASSES the gradient
+__host__ __device__ __forceinline__ float relu_bwd(float g, float y) { return y <= 0.f ? 0.f : g; }
+// (the same gate on stored values: the gradient does not leave its storage type)
+template <typename T> __device__ __forceinline__ T relu_bwd(T g, T y) { return Io<T>::ld(y) <= 0.f ? Io<T>::st(0.f) : g; }
+
+// ---- THE finish kernel behind every pass that leaves per-workgroup column partials (bias gradients, column sums,
+// GroupNorm's gamma / beta gradients): out_y[c] = sum over p < rows of partials[p * row_stride + y * offset1 + c], c < C,
+// for y = blockIdx.y in {0, 1} (the second sum reads the same rows `offset1` floats further on: an interleaved
+// [rows][2][C] layout; a null out_y skips its sum).  A workgroup per kColCh channels, kColRows row lanes per channel:
+// lane r adds rows r, r + kColRows, ... in order, then the lane sums are added in lane order through LDS — a fixed order,
+// and 32x shorter dependent chains than one thread per channel (which took 156 us for 1024 partial rows).
+constexpr int kColCh = 32, kColRows = 32;
+static __global__ void __launch_bounds__(kColCh * kColRows)
+column_partials_finish_kernel(const float* __restrict__ partials, float* __restrict__ out0, float* __restrict__ out1, int C,
+                              int64_t rows, int64_t row_stride, int64_t offset1) {
+  __shared__ float red[kColRows][kColCh + 1];
+  float* out = blockIdx.y ? out1 : out0;
+  if (!out) return;                                          // (uniform over the workgroup)
+  const int cl = threadIdx.x % kColCh, r = threadIdx.x / kColCh;
+  const int c = static_cast<int>(blockIdx.x) * kColCh + cl;
+  const float* col = partials + blockIdx.y * offset1 + c;
+  float s = 0.f;
+  if (c < C)
+    for (int64_t p = r; p < rows; p += kColRows) s += col[p * row_stride];
+  red[r][cl] = s;
+  __syncthreads();
+  if (r == 0 && c < C) {
+    float t = red[0][cl];
+    for (int q = 1; q < kColRows; ++q) t += red[q][cl];
+    out[c] = t;
+  }
+}
+// one sum: out1 = nullptr (a single row of workgroups)
+static inline int column_partials_finish(const float* partials, float* out0, float* out1, int C, int64_t rows, int64_t row_stride,
+                                         int64_t offset1, hipStream_t st) {
+  hipLaunchKernelGGL(column_partials_finish_kernel, dim3(static_cast<unsigned>(ceil_div64(C, kColCh)), out1 ? 2 : 1),
+                     dim3(kColCh * kColRows), 0, st, partials, out0, out1, C, rows, row_stride, offset1);
+  return launch_status();
+}

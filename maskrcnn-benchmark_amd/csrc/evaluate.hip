@@ -11,7 +11,7 @@
 // its rows and columns, iou_offset [P + 1] (int64) its D_p x G_p row-major matrix; a flat pair index finds its problem by
 // bisection of iou_offset.  The caller sizes every array from the same offsets; a pair index outside its problem's matrix
 // (inconsistent offsets) writes 0 and reads nothing.
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -20,12 +20,6 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kPackUnroll = 4;        // words of a plane a wave has in flight
 constexpr int kPackItems = 32;        // words per wave the grid of detops_mask_pack is sized for
 constexpr int kMaxGt = DETOPS_EVAL_MAX_GT;
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
-  return v;                           // lane 0 holds the sum
-}
 
 // the problem that owns flat pair `idx`: the last p with iou_offset[p] <= idx (problems without pairs own nothing)
 __device__ __forceinline__ int problem_of(const int64_t* __restrict__ iou_offset, int P, int64_t idx) {
@@ -151,7 +145,7 @@ mask_pair_counts_kernel(const detops_u64* __restrict__ dt_words, const int64_t* 
           const int64_t w = static_cast<int64_t>(r0 + i / nw) * WW + c0 + i % nw;
           acc += __popcll(a[w] & b[w]);
         }
-        result = wave_sum(acc);
+        result = wave_sum(acc);               // (valid in lane 0, the lane that writes)
       }
     }
   }

@@ -15,7 +15,7 @@
 // reference formula to ~1e-7 absolute (tests: rtol 1e-4, atol 1e-6 vs the oracle restatement).
 #include <float.h>
 
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -140,13 +140,8 @@ focal_kernel(const float* __restrict__ logits, const int32_t* __restrict__ targe
   }
   if (MODE == 2 || MODE == 4) {
     __shared__ float wsum[kBlock / kWave];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) lsum += __shfl_down(lsum, off);
-    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = lsum;
-    __syncthreads();
+    const float s = block_sum<kBlock>(lsum, wsum);
     if (threadIdx.x == 0) {
-      float s = 0.f;
-      for (int j = 0; j < kBlock / kWave; ++j) s += wsum[j];
       // one atomic per workgroup, spread over `nslots` words: ~2000 workgroups finishing together on
       // ONE word serialise in L2 (~12 ns each = a 25 us tail on a 50 us kernel)
       if (MODE == 4) sum_out[blockIdx.x] = s;
@@ -156,22 +151,15 @@ focal_kernel(const float* __restrict__ logits, const int32_t* __restrict__ targe
 }
 
 // Stage 2 of the two-stage sum: one workgroup adds the per-workgroup sums in a fixed order (thread t takes
-// partial[t], partial[t + 256], ...; then a fixed shuffle tree) — the result is bit-reproducible run to run, which
+// partial[t], partial[t + 256], ...; then block_sum) — the result is bit-reproducible run to run, which
 // the atomic form is not.
 __global__ void __launch_bounds__(kBlock)
 focal_sum_reduce_kernel(const float* __restrict__ partial, int n, float* __restrict__ out) {
   __shared__ float wsum[kBlock / kWave];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += kBlock) s += partial[i];
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_down(s, off);
-  if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int j = 0; j < kBlock / kWave; ++j) t += wsum[j];
-    out[0] = t;
-  }
+  s = block_sum<kBlock>(s, wsum);
+  if (threadIdx.x == 0) out[0] = s;
 }
 
 constexpr int kMaxBlocks = kNumCU * 8;

@@ -14,6 +14,28 @@ namespace {
 
 constexpr int kThreads = 256;
 
+// ---- the per-element bodies, written once for both layouts (the kernels below differ in indexing only).  `r` / `y` come
+// by reference: without a residual / ReLU the caller's vector was never loaded and the body does not read it.
+// forward: [relu]( x * s + b [+ r] )
+template <typename T, bool kRelu, bool kRes>
+__device__ __forceinline__ T fbn_fwd_elem(T x, float s, float b, const T& r) {
+#pragma clang fp contract(off)
+  float t = Io<T>::ld(x) * s + b;                // torch: (x * scale) + bias, two roundings in fp32
+  if (kRes) t = t + Io<T>::ld(r);
+  if (kRelu) t = relu_fwd(t);
+  return Io<T>::st(t);
+}
+// backward: g = relu ? relu_bwd(gy, y) : gy ;  grad_x = g * s ;  grad_res = g
+template <typename T, bool kRelu>
+__device__ __forceinline__ void fbn_bwd_elem(T gy, const T& y, float s, T& gx, T& gres) {
+  float t = Io<T>::ld(gy);
+  if (kRelu) t = relu_bwd(t, Io<T>::ld(y));
+  float p = t * s;
+  DETOPS_F32_VALUE(p);                           // fp32 product, then the cast: torch's `(g * s).to(T)`
+  gx = Io<T>::st(p);
+  gres = Io<T>::st(t);
+}
+
 // y = [relu]( x * scale[c] + bias[c] [+ residual] )
 template <typename T, int V, bool kRelu, bool kRes>
 __global__ void __launch_bounds__(kThreads)
@@ -35,12 +57,7 @@ frozen_bn_fwd_kernel(const T* __restrict__ x, const float* __restrict__ scale, c
     if (kRes) r = rv[i];
     VT o;
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float t = Io<T>::ld(a.v[j]) * s + b;       // torch: (x * scale) + bias, two roundings in fp32
-      if (kRes) t = t + Io<T>::ld(r.v[j]);
-      if (kRelu) t = t <= 0.f ? 0.f : t;         // torch.relu: NaN stays NaN
-      o.v[j] = Io<T>::st(t);
-    }
+    for (int j = 0; j < V; ++j) o.v[j] = fbn_fwd_elem<T, kRelu, kRes>(a.v[j], s, b, r.v[j]);
     yv[i] = o;
   }
 }
@@ -65,14 +82,7 @@ frozen_bn_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ y, const fl
     if (kRelu) m = yv[i];
     VT ox, orr;
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float t = Io<T>::ld(g.v[j]);
-      if (kRelu && Io<T>::ld(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
-      float p = t * s;
-      DETOPS_F32_VALUE(p);                            // fp32 product, then the cast: torch's `(g * s).to(T)`
-      ox.v[j] = Io<T>::st(p);
-      if (kRes) orr.v[j] = Io<T>::st(t);
-    }
+    for (int j = 0; j < V; ++j) fbn_bwd_elem<T, kRelu>(g.v[j], m.v[j], s, ox.v[j], orr.v[j]);
     xo[i] = ox;
     if (kRes) ro[i] = orr;
   }
@@ -109,12 +119,7 @@ frozen_bn_fwd_nhwc_kernel(const T* __restrict__ x, const float* __restrict__ sca
     if (kRes) r = rv[i];
     VT o;
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float t = Io<T>::ld(a.v[j]) * s[j] + b[j];
-      if (kRes) t = t + Io<T>::ld(r.v[j]);
-      if (kRelu) t = t <= 0.f ? 0.f : t;         // torch.relu: NaN stays NaN
-      o.v[j] = Io<T>::st(t);
-    }
+    for (int j = 0; j < V; ++j) o.v[j] = fbn_fwd_elem<T, kRelu, kRes>(a.v[j], s[j], b[j], r.v[j]);
     yv[i] = o;
   }
 }
@@ -146,14 +151,7 @@ frozen_bn_bwd_nhwc_kernel(const T* __restrict__ gy, const T* __restrict__ y, con
     if (kRelu) m = yv[i];
     VT ox, orr;
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float t = Io<T>::ld(g.v[j]);
-      if (kRelu && Io<T>::ld(m.v[j]) <= 0.f) t = 0.f;   // threshold_backward: passes where y is NaN
-      float p = t * s[j];
-      DETOPS_F32_VALUE(p);
-      ox.v[j] = Io<T>::st(p);
-      if (kRes) orr.v[j] = Io<T>::st(t);
-    }
+    for (int j = 0; j < V; ++j) fbn_bwd_elem<T, kRelu>(g.v[j], m.v[j], s[j], ox.v[j], orr.v[j]);
     xo[i] = ox;
     if (kRes) ro[i] = orr;
   }

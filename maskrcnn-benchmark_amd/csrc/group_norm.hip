@@ -164,7 +164,7 @@ __device__ __forceinline__ Vec<T, V> gn_apply(const Vec<T, V>& a, const Vec<T, V
   for (int j = 0; j < V; ++j) {
     float t = fmaf(Io<T>::ld(a.v[j]) - mu[j], sc[j], be[j]);
     if (res) t = t + Io<T>::ld(r.v[j]);
-    if (relu) t = t <= 0.f ? 0.f : t;          // torch.relu: NaN stays NaN
+    if (relu) t = relu_fwd(t);
     o.v[j] = Io<T>::st(t);
   }
   return o;
@@ -399,7 +399,7 @@ gn_bwd_reduce_kernel(const T* __restrict__ gy, const T* __restrict__ x, const T*
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         float t = Io<T>::ld(g.v[j]);
-        if (relu && !(Io<T>::ld(m.v[j]) > 0.f)) t = 0.f;
+        if (relu) t = relu_bwd(t, Io<T>::ld(m.v[j]));
         s1[j] += t;
         s2[j] += t * ((Io<T>::ld(a.v[j]) - mu[j]) * rs[j]);
       }
@@ -447,29 +447,6 @@ gn_bwd_group_kernel(const float* __restrict__ sums, const float* __restrict__ ga
   if (lane == 0) { ab[ng * 2] = a * inv_m; ab[ng * 2 + 1] = b * inv_m; }
 }
 
-// ---- backward 2/3 b: grad_beta[c] = sum over (n, s) of sums[.][0][c], grad_gamma[c] likewise of sums[.][1][c].  A workgroup
-// per 32 channels, 32 row lanes per channel (lane r adds partial rows r, r + 32, ... in order), then the lanes in order.
-constexpr int kGfCh = 32, kGfRows = 32;
-__global__ void __launch_bounds__(kGfCh * kGfRows)
-gn_bwd_param_kernel(const float* __restrict__ sums, float* __restrict__ grad_gamma, float* __restrict__ grad_beta, int C, int64_t P) {
-  __shared__ float red[kGfRows][kGfCh + 1];
-  const int cl = threadIdx.x % kGfCh, r = threadIdx.x / kGfCh;
-  const int c = static_cast<int>(blockIdx.x) * kGfCh + cl;
-  const int which = blockIdx.y;
-  float* out = which ? grad_gamma : grad_beta;
-  if (!out) return;                                          // (uniform over the workgroup)
-  float t = 0.f;
-  if (c < C)
-    for (int64_t p = r; p < P; p += kGfRows) t += sums[(p * 2 + which) * C + c];
-  red[r][cl] = t;
-  __syncthreads();
-  if (r == 0 && c < C) {
-    float u = red[0][cl];
-    for (int q = 1; q < kGfRows; ++q) u += red[q][cl];
-    out[c] = u;
-  }
-}
-
 // ---- backward 3/3: grad_x = rstd * (gamma * g - A - xhat * B), grad_residual = g
 template <typename T, int V, int E>
 __global__ void __launch_bounds__(kGnThreads)
@@ -510,7 +487,7 @@ gn_bwd_apply_kernel(const T* __restrict__ gy, const T* __restrict__ x, const T* 
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float t = Io<T>::ld(g.v[j]);
-      if (relu && !(Io<T>::ld(m.v[j]) > 0.f)) t = 0.f;
+      if (relu) t = relu_bwd(t, Io<T>::ld(m.v[j]));
       const float d = c1[j] * t - k0[j] - (Io<T>::ld(a.v[j]) - mu[j]) * k1[j];
       ox.v[j] = Io<T>::st(d);
       orr.v[j] = Io<T>::st(t);
@@ -595,9 +572,8 @@ int gn_backward(const void* gy, const void* x, const void* y, const float* gamma
       e = launch_status();
       if (e) return e;
       if (ggamma || gbeta) {
-        hipLaunchKernelGGL(gn_bwd_param_kernel, dim3(static_cast<unsigned>(ceil_div64(C, kGfCh)), 2), dim3(kGfCh * kGfRows), 0, st, sums,
-                           ggamma, gbeta, C, static_cast<int64_t>(N) * g.S);
-        e = launch_status();
+        // backward 2/3 b: grad_beta[c] = sum over (n, s) of sums[.][0][c], grad_gamma[c] likewise of sums[.][1][c]
+        e = column_partials_finish(sums, gbeta, ggamma, C, static_cast<int64_t>(N) * g.S, 2 * C, C, st);
         if (e) return e;
       }
       hipLaunchKernelGGL((gn_bwd_apply_kernel<T, V, E>), grid, block, 0, st, gp, xp, yp, gamma, mean, rstd, ab, xo, ro, HW, C, G, g.S, R,

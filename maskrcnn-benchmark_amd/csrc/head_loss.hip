@@ -19,22 +19,17 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / kWave;
 
 // #labels with lo <= label < hi — the SAME predicate the loss rows use, so that a malformed label (>= #classes) drops out
-// of the sum and of its normaliser alike; counted by the whole workgroup (every thread returns the count)
+// of the sum and of its normaliser alike; counted by the whole workgroup (every thread returns the count; s_red is free
+// again on return)
 __device__ __forceinline__ float block_count_in(const int64_t* __restrict__ labels, int n, int64_t lo, int64_t hi,
-                                                float* s_red) {
+                                                float (&s_red)[kBlock / kWave]) {
   float c = 0.f;
   for (int i = threadIdx.x; i < n; i += kBlock) c += (labels[i] >= lo && labels[i] < hi) ? 1.f : 0.f;
-  c = wave_sum_all(c);
-  if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = c;
+  c = block_sum<kBlock>(c, s_red);
   __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int j = 0; j < kWavesPerBlock; ++j) t += s_red[j];
-  __syncthreads();
-  return t;
+  return c;
 }
 
 // One wave per sampled ROI.  partial[r] = {cross-entropy of row r (0 when ignored), smooth-L1 of row r (0 unless positive)};
@@ -43,10 +38,10 @@ __global__ void __launch_bounds__(kBlock)
 fastrcnn_loss_kernel(const float* __restrict__ logits, const float* __restrict__ box, const int64_t* __restrict__ labels,
                      const float* __restrict__ targets, int R, int C, int D, int agnostic, float beta,
                      float* __restrict__ grad_logits, float* __restrict__ grad_box, float* __restrict__ partial) {
-  __shared__ float s_red[kWavesPerBlock];
+  __shared__ float s_red[kBlock / kWave];
   const float inv = 1.f / fmaxf(block_count_in(labels, R, 0, C, s_red), 1.f);
   const int lane = threadIdx.x & (kWave - 1);
-  const int r = blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+  const int r = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
   if (r >= R) return;
   const int64_t label = labels[r];
   const float* x = logits + static_cast<size_t>(r) * C;
@@ -87,22 +82,14 @@ fastrcnn_loss_kernel(const float* __restrict__ logits, const float* __restrict__
 __global__ void __launch_bounds__(kBlock)
 head_loss_finish_kernel(const float* __restrict__ partial, int rows, int width, const int64_t* __restrict__ labels, int n,
                         int64_t lo, int64_t hi, float per, float* __restrict__ out) {
-  __shared__ float s_red[kWavesPerBlock];
-  __shared__ float s_sum[2][kWavesPerBlock];
+  __shared__ float s_red[kBlock / kWave];
+  __shared__ float s_sum[2][kBlock / kWave];
   const float inv = 1.f / fmaxf(block_count_in(labels, n, lo, hi, s_red) * per, 1.f);
   float v[2] = {0.f, 0.f};
   for (int i = threadIdx.x; i < rows; i += kBlock)
     for (int k = 0; k < width; ++k) v[k] += partial[i * width + k];
-  for (int k = 0; k < 2; ++k) {
-    const float w = wave_sum(v[k]);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_sum[k][threadIdx.x / kWave] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < width) {
-    float t = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) t += s_sum[threadIdx.x][j];
-    out[threadIdx.x] = t * inv;
-  }
+  block_sum<kBlock>(v, s_sum);
+  if (threadIdx.x < width) out[threadIdx.x] = (threadIdx.x ? v[1] : v[0]) * inv;
 }
 
 // grid (P, kMaskSplit): workgroup (p, y) writes the gradient of the class planes c = y, y + kMaskSplit, ... of ROI p —
@@ -112,7 +99,7 @@ constexpr int kMaskSplit = 8;
 __global__ void __launch_bounds__(kBlock)
 mask_loss_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ targets,
                  int P, int C, int S, float* __restrict__ grad, float* __restrict__ partial) {
-  __shared__ float s_red[kWavesPerBlock];
+  __shared__ float s_red[kBlock / kWave];
   const float inv = 1.f / fmaxf(block_count_in(labels, P, 1, C, s_red) * static_cast<float>(S), 1.f);
   const int p = blockIdx.x;
   const int64_t label = labels[p];
@@ -136,14 +123,8 @@ mask_loss_kernel(const float* __restrict__ logits, const int64_t* __restrict__ l
     }
   }
   if (static_cast<int>(blockIdx.y) != own % kMaskSplit) return;      // one workgroup per ROI reports (0 for a non-positive)
-  loss = wave_sum_all(loss);
-  if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = loss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) t += s_red[j];
-    partial[p] = t;
-  }
+  loss = block_sum<kBlock>(loss, s_red);
+  if (threadIdx.x == 0) partial[p] = loss;
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -170,7 +151,7 @@ DETOPS_API int detops_fastrcnn_loss_f32(const float* class_logits, const float* 
     return DETOPS_EINVAL;
   hipStream_t st = as_stream(stream);
   float* partial = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(fastrcnn_loss_kernel, dim3((R + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, class_logits,
+  hipLaunchKernelGGL(fastrcnn_loss_kernel, dim3((R + kBlock / kWave - 1) / (kBlock / kWave)), dim3(kBlock), 0, st, class_logits,
                      box_regression, labels, regression_targets, R, C, D, cls_agnostic, beta, grad_logits, grad_box, partial);
   hipLaunchKernelGGL(head_loss_finish_kernel, dim3(1), dim3(kBlock), 0, st, partial, R, 2, labels, R,
                      static_cast<int64_t>(0), static_cast<int64_t>(C), 1.f, losses2);

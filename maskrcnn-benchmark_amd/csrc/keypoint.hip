@@ -14,12 +14,11 @@
 // heatmap, then cv2.resize + argmax in a Python loop over the detections).
 #include <cmath>
 
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / kWave;
 
 // ---------------------------------------------------------------------------------------------------------- targets
 // torch's `.floor().long()` of an fp32 value: NaN / inf / out-of-range convert to INT64_MIN (x86 cvttss2si), i.e. invalid
@@ -75,18 +74,11 @@ keypoint_targets_kernel(const float* __restrict__ boxes, const int64_t* __restri
 // One workgroup counts the valid rows once: inv_count[0] = 1 / max(#valid, 1), the normaliser without a host read
 __global__ void __launch_bounds__(kBlock)
 keypoint_loss_count_kernel(const unsigned char* __restrict__ valid, int n, float* __restrict__ inv_count) {
-  __shared__ float s_red[kWavesPerBlock];
+  __shared__ float s_red[kBlock / kWave];
   float c = 0.f;
   for (int i = threadIdx.x; i < n; i += kBlock) c += valid[i] ? 1.f : 0.f;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) c += __shfl_down(c, off);
-  if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) t += s_red[j];
-    inv_count[0] = 1.f / fmaxf(t, 1.f);
-  }
+  c = block_sum<kBlock>(c, s_red);
+  if (threadIdx.x == 0) inv_count[0] = 1.f / fmaxf(c, 1.f);
 }
 
 // (max, sum of exp(x - max)) pairs merged; an empty side (max = -inf) contributes nothing
@@ -106,7 +98,7 @@ keypoint_loss_kernel(const float* __restrict__ logits, int64_t lsP, int64_t lsK,
                      const int64_t* __restrict__ heat, const unsigned char* __restrict__ valid, int K, int H, int W,
                      const float* __restrict__ inv_count, float* __restrict__ grad, int64_t gsP, int64_t gsK, int64_t gsH,
                      int64_t gsW, float* __restrict__ partial) {
-  __shared__ float s_m[kWavesPerBlock], s_s[kWavesPerBlock];
+  __shared__ float s_m[kBlock / kWave], s_s[kBlock / kWave];
   __shared__ float s_lse;
   const int r = blockIdx.x;
   const int p = r / K, k = r % K;
@@ -132,7 +124,7 @@ keypoint_loss_kernel(const float* __restrict__ logits, int64_t lsP, int64_t lsK,
   __syncthreads();
   if (t == 0) {
     float M = s_m[0], sum = s_s[0];
-    for (int j = 1; j < kWavesPerBlock; ++j) lse_merge(M, sum, s_m[j], s_s[j]);
+    for (int j = 1; j < kBlock / kWave; ++j) lse_merge(M, sum, s_m[j], s_s[j]);
     const float lse = M + logf(sum);
     s_lse = lse;
     partial[r] = lse - x[(tg / W) * lsH + (tg % W) * lsW];
@@ -194,18 +186,11 @@ keypoint_loss_roi_kernel(const float* __restrict__ logits, int64_t lsP, int64_t 
 __global__ void __launch_bounds__(kBlock)
 keypoint_loss_finish_kernel(const float* __restrict__ partial, int n, const float* __restrict__ inv_count,
                             float* __restrict__ out) {
-  __shared__ float s_red[kWavesPerBlock];
+  __shared__ float s_red[kBlock / kWave];
   float v = 0.f;
   for (int i = threadIdx.x; i < n; i += kBlock) v += partial[i];
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
-  if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) tot += s_red[j];
-    out[0] = tot * inv_count[0];
-  }
+  v = block_sum<kBlock>(v, s_red);
+  if (threadIdx.x == 0) out[0] = v * inv_count[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------- decoding
@@ -244,8 +229,8 @@ heatmaps_to_keypoints_kernel(const float* __restrict__ maps, int64_t sN, int64_t
                              float* __restrict__ scores) {
 #pragma clang fp contract(off)
   __shared__ float s_map[kMaxMap];
-  __shared__ float s_v[kWavesPerBlock];
-  __shared__ int64_t s_i[kWavesPerBlock];
+  __shared__ float s_v[kBlock / kWave];
+  __shared__ int64_t s_i[kBlock / kWave];
   const int n = blockIdx.x / K, k = blockIdx.x % K;
   const float* src = maps + n * sN + k * sK;
   for (int i = threadIdx.x; i < H * W; i += kBlock) s_map[i] = src[(i / W) * sH + (i % W) * sW];
@@ -286,7 +271,7 @@ heatmaps_to_keypoints_kernel(const float* __restrict__ maps, int64_t sN, int64_t
   if (threadIdx.x != 0) return;
   best = s_v[0];
   bidx = s_i[0];
-  for (int j = 1; j < kWavesPerBlock; ++j)
+  for (int j = 1; j < kBlock / kWave; ++j)
     if (better(s_v[j], s_i[j], best, bidx)) { best = s_v[j]; bidx = s_i[j]; }
   if (bidx == INT64_MAX) bidx = 0;   // every value -inf: numpy's argmax is 0
   const int64_t xint = bidx % ow, yint = bidx / ow;

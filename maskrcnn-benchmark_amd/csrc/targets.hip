@@ -153,37 +153,31 @@ __global__ void __launch_bounds__(kBlock)
 sampler_count_kernel(const T* __restrict__ labels, int n, int32_t* __restrict__ partial /* [N, 2, gridDim.x] */,
                      int32_t* __restrict__ nsurv /* [N, 2] */) {
   const int row = blockIdx.y;
-  int c0 = 0, c1 = 0;
+  int c[2] = {0, 0};                        // negatives, positives
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-    const int c = label_class(labels[static_cast<size_t>(row) * n + i]);
-    c0 += c == 0;
-    c1 += c == 1;
+    const int cls = label_class(labels[static_cast<size_t>(row) * n + i]);
+    c[0] += cls == 0;
+    c[1] += cls == 1;
   }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) { c0 += __shfl_down(c0, off); c1 += __shfl_down(c1, off); }
   __shared__ int s_c[2][kBlock / kWave];
-  if ((threadIdx.x & (kWave - 1)) == 0) { s_c[0][threadIdx.x / kWave] = c0; s_c[1][threadIdx.x / kWave] = c1; }
-  __syncthreads();
+  block_sum<kBlock>(c, s_c);
   if (threadIdx.x < 2) {
-    int t = 0;
-    for (int w = 0; w < kBlock / kWave; ++w) t += s_c[threadIdx.x][w];
-    partial[(static_cast<size_t>(row) * 2 + threadIdx.x) * gridDim.x + blockIdx.x] = t;
+    partial[(static_cast<size_t>(row) * 2 + threadIdx.x) * gridDim.x + blockIdx.x] = threadIdx.x ? c[1] : c[0];
     if (blockIdx.x == 0) nsurv[row * 2 + threadIdx.x] = 0;
   }
 }
 
-// a row's class totals from the count kernel's partials (whole workgroup; result broadcast through LDS)
-__device__ __forceinline__ void sampler_totals(const int32_t* __restrict__ partial, int row, int nblocks, int* s_tot, int& n_neg, int& n_pos) {
-  if (threadIdx.x < 2 * kWave) {            // wave 0: negatives, wave 1: positives
-    const int cls = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
-    int t = 0;
-    for (int i = lane; i < nblocks; i += kWave) t += partial[(static_cast<size_t>(row) * 2 + cls) * nblocks + i];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) t += __shfl_down(t, off);
-    if (lane == 0) s_tot[cls] = t;
+// a row's class totals from the count kernel's partials (a whole workgroup of kThreads; every thread gets them)
+template <int kThreads>
+__device__ __forceinline__ void sampler_totals(const int32_t* __restrict__ partial, int row, int nblocks,
+                                               int (&s_tot)[2][kThreads / kWave], int& n_neg, int& n_pos) {
+  int t[2] = {0, 0};
+  for (int i = threadIdx.x; i < nblocks; i += kThreads) {
+    t[0] += partial[static_cast<size_t>(row) * 2 * nblocks + i];
+    t[1] += partial[(static_cast<size_t>(row) * 2 + 1) * nblocks + i];
   }
-  __syncthreads();
-  n_neg = s_tot[0]; n_pos = s_tot[1];
+  block_sum<kThreads>(t, s_tot);
+  n_neg = t[0]; n_pos = t[1];
 }
 
 struct SamplerPlan {
@@ -209,9 +203,9 @@ sampler_filter_kernel(const T* __restrict__ labels, SamplerPlan P, const int32_t
                       int32_t* __restrict__ nsurv /* [N, 2] */, unsigned long long* __restrict__ surv /* [N, 2, cap] */,
                       uint8_t* __restrict__ pos_mask, uint8_t* __restrict__ neg_mask) {
   const int row = blockIdx.y;
-  __shared__ int s_tot[2];
+  __shared__ int s_tot[2][kBlock / kWave];
   int n_neg, n_pos;
-  sampler_totals(partial, row, P.count_blocks, s_tot, n_neg, n_pos);
+  sampler_totals<kBlock>(partial, row, P.count_blocks, s_tot, n_neg, n_pos);
   const int k_pos = min(n_pos, P.max_pos);
   const int k_neg = min(min(n_neg, P.B), P.B - k_pos);
   const unsigned thr_pos = class_threshold(n_pos, k_pos), thr_neg = class_threshold(n_neg, k_neg);
@@ -245,17 +239,18 @@ sampler_filter_kernel(const T* __restrict__ labels, SamplerPlan P, const int32_t
 }
 
 // one workgroup per (row, class): sort the class's survivors by (key, index) in LDS, keep the quota
-__global__ void __launch_bounds__(1024)
+constexpr int kSortBlock = 1024;
+__global__ void __launch_bounds__(kSortBlock)
 sampler_finish_kernel(SamplerPlan P, const int32_t* __restrict__ partial, const int32_t* __restrict__ nsurv,
                       const unsigned long long* __restrict__ surv, uint8_t* __restrict__ pos_mask,
                       uint8_t* __restrict__ neg_mask, int64_t* __restrict__ idx /* [N, B] nullable */,
                       uint8_t* __restrict__ idx_valid /* [N, B] nullable */) {
   DETOPS_DYNAMIC_LDS(unsigned long long, keys);
-  __shared__ int s_tot[2];
+  __shared__ int s_tot[2][kSortBlock / kWave];
   const int row = blockIdx.x;
   const int c = 1 - static_cast<int>(blockIdx.y);   // y = 0: positives
   int n_neg, n_pos;
-  sampler_totals(partial, row, P.count_blocks, s_tot, n_neg, n_pos);
+  sampler_totals<kSortBlock>(partial, row, P.count_blocks, s_tot, n_neg, n_pos);
   const int k_pos = min(n_pos, P.max_pos);
   const int k_neg = min(min(n_neg, P.B), P.B - k_pos);
   const int ns = min(nsurv[row * 2 + c], P.cap);
@@ -387,7 +382,7 @@ int run_sampler(const void* labels, int N, int n, int B, int max_pos, unsigned l
   hipLaunchKernelGGL(sampler_filter_kernel<T>, grid, dim3(kBlock), 0, st, lab, P, counts, nsurv, surv, pos_mask, neg_mask);
   int npad = 2;
   while (npad < l.cap) npad <<= 1;
-  hipLaunchKernelGGL(sampler_finish_kernel, dim3(static_cast<unsigned>(N), 2), dim3(1024), npad * sizeof(unsigned long long), st,
+  hipLaunchKernelGGL(sampler_finish_kernel, dim3(static_cast<unsigned>(N), 2), dim3(kSortBlock), npad * sizeof(unsigned long long), st,
                      P, counts, nsurv, surv, pos_mask, neg_mask, idx, idx_valid);
   return launch_status();
 }
@@ -477,18 +472,10 @@ rpn_loss_kernel(RpnLevels L, int A, const float* __restrict__ anchors, const int
     for (int k = 0; k < 4; ++k) gbox[o4 + static_cast<size_t>(k) * plane] = g4[k];
   }
   __shared__ float red[3][kBlock / kWave];
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    s_obj += __shfl_down(s_obj, off); s_box += __shfl_down(s_box, off); s_cnt += __shfl_down(s_cnt, off);
-  }
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-    red[0][threadIdx.x / kWave] = s_obj; red[1][threadIdx.x / kWave] = s_box; red[2][threadIdx.x / kWave] = s_cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    float v = 0.f;
-    for (int j = 0; j < kBlock / kWave; ++j) v += red[threadIdx.x][j];
-    partial[blockIdx.x * 3 + threadIdx.x] = v;
+  float v[3] = {s_obj, s_box, s_cnt};
+  block_sum<kBlock>(v, red);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 3] = v[0]; partial[blockIdx.x * 3 + 1] = v[1]; partial[blockIdx.x * 3 + 2] = v[2];
   }
 }
 
@@ -500,20 +487,11 @@ rpn_loss_finish_kernel(const float* __restrict__ partial, int nblocks, float* __
   for (int i = threadIdx.x; i < nblocks; i += kBlock) {
     v[0] += partial[i * 3]; v[1] += partial[i * 3 + 1]; v[2] += partial[i * 3 + 2];
   }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    v[0] += __shfl_down(v[0], off); v[1] += __shfl_down(v[1], off); v[2] += __shfl_down(v[2], off);
-  }
-  if ((threadIdx.x & (kWave - 1)) == 0)
-    for (int k = 0; k < 3; ++k) red[k][threadIdx.x / kWave] = v[k];
-  __syncthreads();
+  block_sum<kBlock>(v, red);
   if (threadIdx.x == 0) {
-    float t[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < kBlock / kWave; ++j)
-      for (int k = 0; k < 3; ++k) t[k] += red[k][j];
-    const float inv = 1.f / fmaxf(t[2], 1.f);
-    out3[0] = t[0] * inv;
-    out3[1] = t[1] * inv;
+    const float inv = 1.f / fmaxf(v[2], 1.f);
+    out3[0] = v[0] * inv;
+    out3[1] = v[1] * inv;
     out3[2] = inv;
   }
 }
@@ -743,13 +721,7 @@ head_rows_write_kernel(HeadLevels L, int A, int N, int64_t total, const int* __r
   __shared__ int red[kBlock / kWave];
   int before = 0;   // rows of the workgroups in front of this one
   for (int b = threadIdx.x; b < static_cast<int>(blockIdx.x); b += kBlock) before += block_counts[b];
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) before += __shfl_down(before, off);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = before;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int k = 0; k < kBlock / kWave; ++k) base += red[k];
+  int base = block_sum<kBlock>(before, red);
   for (int it = 0; it < kHeadItems; ++it) {
     const int64_t j = (static_cast<int64_t>(blockIdx.x) * kHeadItems + it) * kBlock + threadIdx.x;
     HeadRow r;
@@ -788,7 +760,7 @@ head_hidden_kernel(HeadLevels L, int C, const HeadRow* __restrict__ rows, const 
     float v = R.g[0] * wc[c];
 #pragma unroll
     for (int k = 0; k < 4; ++k) v += R.g[1 + k] * wb[k * C + c];
-    G[static_cast<size_t>(r) * C + c] = (tv <= 0.f) ? 0.f : v;   // bias_act's ReLU rule: a NaN activation passes the gradient
+    G[static_cast<size_t>(r) * C + c] = relu_bwd(v, tv);
     Tm[static_cast<size_t>(r) * C + c] = tv;
   }
   if (threadIdx.x < 9) {

@@ -20,6 +20,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import torch_refs
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -211,6 +213,45 @@ def test_statistics_of_shifted_data_stay_linear_in_mean_over_sigma(shape, mean, 
 @pytest.mark.parametrize("shape", [(2, 64, 32, 32, 32), (2, 64, 32, 25, 41)], ids=["sample", "split"])
 def test_shifted_backward_on_each_side_of_the_routing_threshold(shape):
     _run(shape, torch.float32, True, True, seed=9, mean=100.0, std=1.0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16", "bf16"])
+def test_fused_relu_follows_torch_relu_on_a_non_finite_residual(dtype):
+    """The GroupNorm analogue of torch_refs.check_fused_relu_non_finite: NaN, +-inf and -0.0 arrive through the RESIDUAL only
+    (its patterns there), so the group statistics stay finite.  Forward: torch.relu — y is NaN exactly where the residual is,
+    +inf under a +inf residual, 0 under a -inf one.  Backward: the gate is aten.threshold_backward(gy, y, 0), which PASSES the
+    gradient where y is NaN (as F.group_norm + relu does under DETOPS_GROUP_NORM=torch): grad_residual equals it exactly, and
+    grad_x / grad_gamma / grad_beta meet the module's backward rule against fp64 fed the same masked gradient."""
+    C_ = _C()
+    N, C, G, H, W = 2, 8, 2, 4, 6
+    inf, nan = float("inf"), float("nan")
+    x_d, x = _cl((N, C, H, W), dtype, 21)
+    res = torch.randn(N, C, H, W, generator=torch.Generator().manual_seed(22))
+    res[:, :, 1, :4] = torch.tensor([-inf, inf, nan, inf])
+    res[:, :, 2, :2] = torch.tensor([-0.0, -inf])
+    res = res.to(dtype)
+    res_d = res.to(DEV).contiguous(memory_format=CL)
+    gamma, beta = _affine(C, 23)
+    y_d, mu, rs = C_.group_norm_forward(x_d, G, gamma, beta, EPS, res_d, True)
+    y = y_d.cpu()
+    _check_statistics(x, mu, rs, G)
+    assert torch.equal(y.isnan(), res.isnan()) and int(y.isnan().sum()) == N * C
+    assert bool((y[res == inf] == inf).all()) and bool((y[res == -inf] == 0).all()) and not bool(torch.isinf(y[res.isfinite()]).any())
+    gy_d, gy = _cl((N, C, H, W), dtype, 24)
+    got = dict(zip(("grad_x", "grad_residual", "grad_gamma", "grad_beta"),
+                   C_.group_norm_backward(gy_d, x_d, y_d, G, gamma, mu, rs, True, True, True, True)))
+    want = torch.ops.aten.threshold_backward(gy.float(), y.float(), 0)
+    assert bool((want[y.isnan()] == gy.float()[y.isnan()]).all()) and bool((want[y == 0] == 0).all())
+    torch_refs._exact(got["grad_residual"].cpu(), want.to(dtype), "group_norm grad_residual")
+    masked = want.double()
+    ref = _host_backward(x, res, gamma, beta, masked, G, torch.float64)
+    aten = _host_backward(x, res, gamma, beta, masked, G, torch.float32)
+    floor = 0.0 if dtype == torch.float32 else torch.finfo(dtype).eps
+    for name in ("grad_x", "grad_gamma", "grad_beta"):
+        mine, theirs = _rel(got[name].cpu(), ref[name]), _rel(aten[name], ref[name])
+        allowed = max(8 * theirs, floor)
+        print("  %s: error %.3g, ATen fp32 %.3g, allowed %.3g" % (name, mine, theirs, allowed))
+        assert mine <= allowed, (name, mine, theirs, allowed)
 
 
 def test_host_rule_equals_the_library_rule():
