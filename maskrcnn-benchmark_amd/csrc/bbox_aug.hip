@@ -16,7 +16,7 @@
 //   offsets  one workgroup: a fixed-shape scan over the segment lengths -> seg_offsets, the total and the longest segment
 //   write    the count pass again; position = seg_offsets[segment] + prefix of the (tile, wave) + candidates of the class
 //            seen so far by the wave + candidates of the class on lower lanes of this step
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -83,16 +83,6 @@ __global__ void __launch_bounds__(kBlock) bbox_aug_count_kernel(const float* __r
   if (k.sub == 0 && k.col < C) cnt[cnt_index(C, per, k.col, k.slot)] = c;
 }
 
-// inclusive scan over a wave
-__device__ __forceinline__ int wave_inclusive_scan(int v) {
-  const int lane = threadIdx.x % kWave;
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
 // a wave per segment: cnt[segment][0 .. per) -> its exclusive prefix, in place; seg_len[segment] = the sum
 __global__ void __launch_bounds__(kBlock) bbox_aug_prefix_kernel(int32_t* __restrict__ cnt, int S, int C, int per,
                                                                  int32_t* __restrict__ seg_len) {
@@ -100,48 +90,23 @@ __global__ void __launch_bounds__(kBlock) bbox_aug_prefix_kernel(int32_t* __rest
   if (s >= S) return;                                  // wave-uniform
   const int n = s / (C - 1), j = 1 + s % (C - 1);
   int32_t* p = cnt + (static_cast<int64_t>(n) * C + j) * per;
-  int carry = 0;
-  for (int base = 0; base < per; base += kWave) {      // uniform trip count: shuffles inside
-    const int i = base + lane;
-    const int v = i < per ? p[i] : 0;
-    const int incl = wave_inclusive_scan(v);
-    if (i < per) p[i] = carry + incl - v;
-    carry += __shfl(incl, kWave - 1);
-  }
-  if (lane == 0) seg_len[s] = carry;
-}
-
-// inclusive scan over the workgroup (kScanBlock threads); *total: the sum over all threads
-__device__ __forceinline__ int block_inclusive_scan(int v, int* wave_sums, int* total) {
-  const int lane = threadIdx.x % kWave, w = threadIdx.x / kWave;
-  v = wave_inclusive_scan(v);
-  if (lane == kWave - 1) wave_sums[w] = v;
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int i = 0; i < kScanBlock / kWave; ++i) {
-    const int t = wave_sums[i];
-    before += i < w ? t : 0;
-    all += t;
-  }
-  __syncthreads();                                     // wave_sums is written again by the next call
-  *total = all;
-  return v + before;
+  const int len = scan_tiles<kWave>(per, [&](int i) { return p[i]; }, [&](int i, int before) { p[i] = before; });
+  if (lane == 0) seg_len[s] = len;
 }
 
 __global__ void __launch_bounds__(kScanBlock) bbox_aug_offsets_kernel(const int32_t* __restrict__ seg_len, int S,
                                                                       int32_t* __restrict__ seg_offsets, int32_t* __restrict__ totals) {
   __shared__ int wave_sums[kScanBlock / kWave];
-  int carry = 0, longest = 0;
-  for (int base = 0; base < S; base += kScanBlock) {   // uniform trip count: barriers inside
-    const int s = base + threadIdx.x;
-    const int len = s < S ? seg_len[s] : 0;
-    int all;
-    const int incl = block_inclusive_scan(len, wave_sums, &all);
-    if (s < S) seg_offsets[s] = carry + incl - len;
-    carry += all;
-    longest = len > longest ? len : longest;
-  }
-  // the longest segment: a max over the workgroup through the scan's scratch
+  int longest = 0;
+  const int carry = scan_tiles<kScanBlock>(
+      S,
+      [&](int s) {
+        const int len = seg_len[s];
+        longest = len > longest ? len : longest;
+        return len;
+      },
+      [&](int s, int before) { seg_offsets[s] = before; }, wave_sums);
+  // the longest segment: a max over the workgroup through the scan's scratch (free again: scan_tiles ends on a barrier)
   for (int d = kWave / 2; d >= 1; d >>= 1) {
     const int u = __shfl_down(longest, d);
     longest = u > longest ? u : longest;

@@ -1,9 +1,12 @@
 // detops_dtype.h — what the elementwise and loss kernels share: storage-type I/O, 16-byte vectors, the host-side step from
 // a run-time dtype code / vector width / flag to a template argument, the wave and workgroup sums in the library's one
-// fixed order, the finish kernel for column partials, and the fused ReLU rule.  Only helpers with at least two users live here.
+// fixed order, the integer prefix scans (wave, workgroup, carried over tiles) with their one scratch and barrier contract,
+// the lookup in an ascending offsets table, the finish kernel for column partials, and the fused ReLU rule.  Only helpers
+// with at least two users live here.
 #pragma once
 #include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "detops_common.h"
 
@@ -115,6 +118,91 @@ __device__ __forceinline__ T block_sum(T v, T (&scratch)[kThreads / kWave]) {
   T a[1] = {v};
   block_sum<kThreads>(a, reinterpret_cast<T (&)[1][kThreads / kWave]>(scratch));
   return a[0];
+}
+
+// ---- THE inclusive scan of ONE value over the wave, in lane order: lane l gets op(... op(v_0, v_1) ..., v_l); op is +
+// unless given (T = int | int64_t; integers, so the tree's order changes no bit).  The exclusive sum is `incl - v` at the
+// call site, the wave's total is `__shfl(incl, kWave - 1)`.  Every lane of the wave calls it.
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_scan(T v, Op op) {
+  const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const T o = __shfl_up(v, off);
+    if (lane >= off) v = op(v, o);
+  }
+  return v;
+}
+template <typename T> __device__ __forceinline__ T wave_scan(T v) {
+  return wave_scan(v, [](T a, T b) { return a + b; });
+}
+
+// ---- THE scan over a workgroup of kThreads threads, in thread order.  Same contract as block_sum: every thread of the
+// workgroup calls it, in uniform control flow (it holds one barrier); `scratch` is LDS of kThreads / kWave elements, other
+// threads may still be reading it on return, so it (these functions included) may be written again only after a later
+// __syncthreads(), which the caller places (a loop around it: one at the end of the body).
+// The cross-wave half: `wave_total` is the wave's sum in its LAST lane (wave_scan's inclusive value there; a ballot's
+// popcount in every lane); returns the sum of the waves before the caller's own, `total` = the sum of all.
+template <int kThreads, typename T>
+__device__ __forceinline__ T block_scan_base(T wave_total, T* scratch, T& total) {
+  static_assert(kThreads % kWave == 0, "whole waves");
+  const int wave = threadIdx.x / kWave;
+  if ((threadIdx.x & (kWave - 1)) == kWave - 1) scratch[wave] = wave_total;
+  __syncthreads();
+  T base = 0, all = 0;
+#pragma unroll
+  for (int j = 0; j < kThreads / kWave; ++j) {
+    const T t = scratch[j];
+    if (j < wave) base += t;
+    all += t;
+  }
+  total = all;
+  return base;
+}
+// the whole of it: the inclusive sum of v over the threads up to the caller's own (exclusive: `- v` at the call site)
+template <int kThreads, typename T>
+__device__ __forceinline__ T block_scan(T v, T* scratch, T& total) {
+  const T incl = wave_scan(v);
+  return block_scan_base<kThreads>(incl, scratch, total) + incl;
+}
+
+// ---- THE loop that scans an array longer than its tile: elements [0, n) in tiles of kTile, tiles in order with a running
+// carry.  kTile = kWave: the calling wave alone (uniform over the wave; no barrier, no scratch).  kTile = the workgroup's
+// size: block_scan and its contract, with the barrier that frees `scratch` for the next tile at the end of each round
+// (two barriers a round).  load(i) reads element i, store(i, before) gets the sum of the elements in front of i (it may
+// overwrite what load read); the sum of all n is returned to every thread.  T is what load returns.
+template <int kTile, typename I, typename Load, typename Store, typename T = decltype(std::declval<Load>()(I{}))>
+__device__ __forceinline__ T scan_tiles(I n, Load load, Store store, T* scratch = nullptr) {
+  static_assert(kTile % kWave == 0 && (kTile & (kTile - 1)) == 0, "whole waves, a power of two");
+  T carry = 0;
+  for (I base = 0; base < n; base += kTile) {
+    const I i = base + static_cast<I>(threadIdx.x & (kTile - 1));
+    const T v = i < n ? load(i) : T(0);
+    T incl, total;
+    if constexpr (kTile == kWave) {
+      incl = wave_scan(v);
+      total = __shfl(incl, kWave - 1);
+    } else {
+      incl = block_scan<kTile>(v, scratch, total);
+    }
+    if (i < n) store(i, carry + incl - v);
+    carry += total;
+    if constexpr (kTile != kWave) __syncthreads();
+  }
+  return carry;
+}
+
+// ---- THE lookup in an ascending offsets table (global or LDS; int or int64_t): the last m < n with table[m] <= i, 0 when
+// there is none.  Entries without elements share their successor's offset, so the LAST of equal entries owns i.  A
+// bisection that reads table[1 .. n - 1] only and ends after ceil(log2 n) steps whatever the table holds.
+template <typename T, typename I>
+__device__ __forceinline__ int last_at_or_below(const T* table, int n, I i) {
+  int lo = 0, hi = n;                   // table[lo] <= i < table[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (table[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
 }
 
 // ---- THE fused ReLU rule, torch's, for every kernel that folds a ReLU into its epilogue or its backward

@@ -21,16 +21,6 @@ constexpr int kPackUnroll = 4;        // words of a plane a wave has in flight
 constexpr int kPackItems = 32;        // words per wave the grid of detops_mask_pack is sized for
 constexpr int kMaxGt = DETOPS_EVAL_MAX_GT;
 
-// the problem that owns flat pair `idx`: the last p with iou_offset[p] <= idx (problems without pairs own nothing)
-__device__ __forceinline__ int problem_of(const int64_t* __restrict__ iou_offset, int P, int64_t idx) {
-  int lo = 0, hi = P;                 // iou_offset[lo] <= idx < iou_offset[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (iou_offset[mid] <= idx) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 struct Pair {
   int p, d, g;        // problem, detection and ground truth (indices into the sorted arrays), or p = -1
 };
@@ -38,7 +28,7 @@ struct Pair {
 __device__ __forceinline__ Pair pair_of(const int32_t* __restrict__ dt_offset, const int32_t* __restrict__ gt_offset,
                                         const int64_t* __restrict__ iou_offset, int P, int64_t idx) {
   Pair r;
-  r.p = problem_of(iou_offset, P, idx);
+  r.p = last_at_or_below(iou_offset, P, idx);   // the problem that owns flat pair `idx` (problems without pairs own nothing)
   const int d0 = dt_offset[r.p], g0 = gt_offset[r.p];
   const int D = dt_offset[r.p + 1] - d0, G = gt_offset[r.p + 1] - g0;
   const int64_t local = idx - iou_offset[r.p];

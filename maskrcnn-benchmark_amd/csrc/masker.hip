@@ -316,15 +316,7 @@ paste_masks_rle_scan_kernel(RleWorkspace ws, int max_w) {
     const int c = c0 + lane;
     const int v = c < max_w ? col_count[c] : 0;
     const int l = c < max_w ? col_last[c] : -1;
-    int s = v, m = l;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int os = __shfl_up(s, off), om = __shfl_up(m, off);
-      if (lane >= off) {
-        s += os;
-        m = max(m, om);
-      }
-    }
+    const int s = wave_scan(v), m = wave_scan(l, [](int a, int b) { return max(a, b); });
     int m_before = __shfl_up(m, 1);
     if (lane == 0) m_before = -1;
     if (c < max_w) {
@@ -344,19 +336,9 @@ paste_masks_rle_scan_kernel(RleWorkspace ws, int max_w) {
 __global__ void __launch_bounds__(kWave)
 paste_masks_rle_offsets_kernel(RleWorkspace ws, int N, int64_t* __restrict__ run_offset) {
   const int lane = threadIdx.x;
-  int64_t sum = 0;
-  if (lane == 0) run_offset[0] = 0;
-  for (int i0 = 0; i0 < N; i0 += kWave) {
-    const int i = i0 + lane;
-    int64_t s = i < N ? ws.det_runs[i] : 0;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int64_t o = __shfl_up(s, off);
-      if (lane >= off) s += o;
-    }
-    if (i < N) run_offset[i + 1] = sum + s;
-    sum += __shfl(s, kWave - 1);
-  }
+  const int64_t total = scan_tiles<kWave>(
+      N, [&](int i) { return static_cast<int64_t>(ws.det_runs[i]); }, [&](int i, int64_t before) { run_offset[i] = before; });
+  if (lane == 0) run_offset[N] = total;
 }
 
 int check_args(int N, int M, int padding) {

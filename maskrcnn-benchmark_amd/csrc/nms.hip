@@ -30,6 +30,7 @@
 #include <random>
 
 #include "detops_devlib.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -452,8 +453,7 @@ __device__ __forceinline__ void compact_keep(const u64* keptw, u64* flags, int* 
                                              SegView sv, int s, int64_t* __restrict__ keep,
                                              int32_t* __restrict__ num_keep, uint8_t* __restrict__ keep_mask) {
   const int n = sv.n, nb = (n + kWave - 1) / kWave;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  constexpr int kWaves = kScanThreads / kWave;
+  const int tid = threadIdx.x;
   // kept sorted positions -> bitset over original (segment-local) indices
   for (int p = tid; p < n; p += kScanThreads) {
     if ((keptw[p >> 6] >> (p & 63)) & 1ull) {
@@ -472,21 +472,8 @@ __device__ __forceinline__ void compact_keep(const u64* keptw, u64* flags, int* 
   int local = 0;
   for (int j = 0; j < wpt; ++j)
     if (w0 + j < nb) local += __popcll(flags[w0 + j]);
-  int incl = local;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int t = __shfl_up(incl, off);
-    if (lane >= off) incl += t;
-  }
-  if (lane == kWave - 1) wsum[wave] = incl;
-  __syncthreads();
-  int base = 0, total = 0;
-  for (int j = 0; j < kWaves; ++j) {
-    const int v = wsum[j];
-    if (j < wave) base += v;
-    total += v;
-  }
-  int pos = base + incl - local;
+  int total;
+  int pos = block_scan<kScanThreads>(local, wsum, total) - local;
   int64_t* kout = keep + sv.begin;
   for (int j = 0; keep && j < wpt; ++j) {
     if (w0 + j >= nb) break;

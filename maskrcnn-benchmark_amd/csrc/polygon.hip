@@ -15,7 +15,7 @@
 // is zero at every column's start once the crossings clamped to row h are counted; those land on row 0 of the NEXT column
 // and cancel exactly the parity their own column hands over.  Dropping them and taking the prefix parity per column is
 // the same fill, and lets a workgroup own a strip of columns.
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -156,7 +156,7 @@ template <typename Transform>
 __device__ __forceinline__ void fill_polygons(const float2* __restrict__ verts, const int* __restrict__ poly_offset, int p0, int p1,
                                               int V, Transform xf, int c0, int ncols, int h, int hw, uint32_t* tog,
                                               uint32_t* res, EdgeStage* st) {
-  const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+  const int tid = threadIdx.x;
   for (int p = p0; p < p1; ++p) {
     const int v0 = min(max(poly_offset[p], 0), V);
     const int k = min(max(poly_offset[p + 1], v0), V) - v0;
@@ -171,27 +171,12 @@ __device__ __forceinline__ void fill_polygons(const float2* __restrict__ verts, 
         st->edge[tid] = e;
         count = edge_columns(e, c0, ncols).y;
       }
-      int incl = count;
-#pragma unroll
-      for (int off = 1; off < kWave; off <<= 1) {
-        const int o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-      }
-      if (lane == kWave - 1) st->wave_sum[wave] = incl;
-      __syncthreads();
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < kBlock / kWave; ++w) {
-        const int ws = st->wave_sum[w];
-        before += w < wave ? ws : 0;
-        total += ws;
-      }
-      st->start[tid] = before + incl - count;     // threads beyond the chunk: the total
+      int total;
+      st->start[tid] = block_scan<kBlock>(count, st->wave_sum, total) - count;     // threads beyond the chunk: the total
       __syncthreads();
       for (int i = tid; i < total; i += kBlock) {
-        int e = 0;                                 // the last edge with start[e] <= i: edges without crossings share their
-        for (int step = kEdgeChunk / 2; step > 0; step >>= 1)   // start with the next edge that has some
-          if (e + step < n && st->start[e + step] <= i) e += step;
+        // the last edge with start[e] <= i: edges without crossings share their start with the next edge that has some
+        const int e = last_at_or_below(st->start, n, i);
         const int4 edge = st->edge[e];
         const int c = edge_columns(edge, c0, ncols).x + (i - st->start[e]);
         const int r = crossing_row(edge, c, h);

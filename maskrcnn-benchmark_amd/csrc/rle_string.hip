@@ -10,7 +10,7 @@
 // a binary search in run_offset for the thread's first run and a walk from there.  A value's length is a closed form of
 // its bit length, so both passes compute the same lengths and the offsets are plain prefix sums in a fixed order: no
 // atomics, every output byte written exactly once, two runs give identical bytes.
-#include "detops_common.h"
+#include "detops_dtype.h"
 
 namespace {
 
@@ -30,19 +30,6 @@ __device__ __forceinline__ int code_len(int64_t x) {
   const unsigned long long y = static_cast<unsigned long long>(x < 0 ? ~x : x);
   const int bits = y ? 64 - __builtin_clzll(y) : 0;
   return (bits + 5) / 5;
-}
-
-// the last mask m < N with run_offset[m] <= i (masks without runs share their successor's offset: the last one owns i)
-__device__ __forceinline__ int mask_of(const int64_t* __restrict__ ro, int N, int64_t i) {
-  int lo = 0, hi = N - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (ro[mid] <= i)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
 }
 
 struct ThreadRuns {
@@ -65,7 +52,7 @@ __device__ __forceinline__ ThreadRuns load_runs(const int32_t* __restrict__ c, c
     r.first[j] = false;
   }
   if (i0 >= total) return r;
-  int m = mask_of(ro, N, i0);
+  int m = last_at_or_below(ro, N, i0);   // masks without runs share their successor's offset: the last one owns i0
   int64_t start = ro[m];
   int64_t next = m + 1 < N ? ro[m + 1] : INT64_MAX;
 #pragma unroll
@@ -89,30 +76,6 @@ __device__ __forceinline__ ThreadRuns load_runs(const int32_t* __restrict__ c, c
   return r;
 }
 
-// exclusive sum of `v` over the workgroup in thread order, and the workgroup's total (one use per kernel: wave_tot is
-// not protected against a second round)
-template <typename V>
-__device__ __forceinline__ V block_exclusive(V v, V* wave_tot, V& block_total) {
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  V s = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const V o = __shfl_up(s, off);
-    if (lane >= off) s += o;
-  }
-  if (lane == kWave - 1) wave_tot[wave] = s;
-  __syncthreads();
-  V before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const V t = wave_tot[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  block_total = all;
-  return before + s - v;
-}
-
 // chunk_bytes[chunk] = bytes of the chunk; byte_offset[m] = bytes of the chunk in front of mask m's first run, written by
 // the thread that owns that run (for every mask that has its first run, or would have it, at that position)
 __global__ void __launch_bounds__(kBlock)
@@ -122,7 +85,7 @@ rle_string_count_kernel(const int32_t* __restrict__ c, const int64_t* __restrict
   const int64_t i0 = static_cast<int64_t>(blockIdx.x) * kChunk + static_cast<int64_t>(threadIdx.x) * kPer;
   const ThreadRuns r = load_runs(c, ro, N, total, i0);
   int all;
-  int off = block_exclusive(r.sum, wave_tot, all);
+  int off = block_scan<kBlock>(r.sum, wave_tot, all) - r.sum;
   if (threadIdx.x == 0) chunk_bytes[blockIdx.x] = all;
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
@@ -139,30 +102,8 @@ __global__ void __launch_bounds__(kBlock)
 rle_string_offsets_kernel(const int64_t* __restrict__ ro, int N, int64_t total, int64_t nchunks,
                           int64_t* __restrict__ chunk_bytes, int64_t* __restrict__ byte_offset) {
   __shared__ int64_t wave_tot[kWaves];
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  int64_t carry = 0;
-  for (int64_t b0 = 0; b0 < nchunks; b0 += kBlock) {
-    const int64_t b = b0 + threadIdx.x;
-    const int64_t v = b < nchunks ? chunk_bytes[b] : 0;
-    int64_t s = v;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int64_t o = __shfl_up(s, off);
-      if (lane >= off) s += o;
-    }
-    if (lane == kWave - 1) wave_tot[wave] = s;
-    __syncthreads();
-    int64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int64_t t = wave_tot[w];
-      if (w < wave) before += t;
-      all += t;
-    }
-    if (b < nchunks) chunk_bytes[b] = carry + before + s - v;
-    carry += all;
-    __syncthreads();
-  }
+  const int64_t carry = scan_tiles<kBlock>(
+      nchunks, [&](int64_t b) { return chunk_bytes[b]; }, [&](int64_t b, int64_t before) { chunk_bytes[b] = before; }, wave_tot);
   for (int64_t j = threadIdx.x; j <= N; j += kBlock) {
     const int64_t first = ro[j];
     byte_offset[j] = (j == N || first >= total || first < 0) ? carry : chunk_bytes[first / kChunk] + byte_offset[j];
@@ -181,7 +122,7 @@ rle_string_write_kernel(const int32_t* __restrict__ c, const int64_t* __restrict
   const int64_t i0 = static_cast<int64_t>(blockIdx.x) * kChunk + static_cast<int64_t>(threadIdx.x) * kPer;
   const ThreadRuns r = load_runs(c, ro, N, total, i0);
   int all;
-  const int off = block_exclusive(r.sum, wave_tot, all);
+  const int off = block_scan<kBlock>(r.sum, wave_tot, all) - r.sum;
   unsigned char* dst = out + chunk_base[blockIdx.x];
   const int shift = static_cast<int>(reinterpret_cast<uintptr_t>(dst) & 15);
   int p = shift + off;

@@ -684,18 +684,10 @@ __device__ __forceinline__ bool head_row_at(const HeadLevels L, int A, int N, in
 // position of a flagged thread among the flagged threads of the workgroup, and their number
 __device__ __forceinline__ int head_block_rank(bool flag, int* wave_tot, int& total) {
   const unsigned long long m = __ballot(flag);
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  const int lane = threadIdx.x & (kWave - 1);
   const int rank = __popcll(m & ((1ull << lane) - 1ull));
-  __syncthreads();                       // the previous round's readers are done with wave_tot
-  if (lane == 0) wave_tot[w] = __popcll(m);
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < kBlock / kWave; ++k) {
-    if (k < w) before += wave_tot[k];
-    total += wave_tot[k];
-  }
+  const int before = block_scan_base<kBlock>(static_cast<int>(__popcll(m)), wave_tot, total);
+  __syncthreads();                       // wave_tot is free for the next round
   return before + rank;
 }
 

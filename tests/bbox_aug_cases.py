@@ -60,6 +60,14 @@ MERGE_CASES = {
     "nothing_passes": dict(seed=8, C=5, rows=[[40, 3], [0, 130]], frames=_frames(2, 2), flips=[0, 1], pass_rate=0.0),
     "no_rows": dict(seed=9, C=5, rows=[[0, 0], [0, 0]], frames=_frames(2, 2), flips=[0, 1]),
     "class_agnostic": dict(seed=10, C=6, rows=[[65, 130], [33, 0]], frames=_frames(2, 2), flips=[0, 1], agnostic=True),
+    # the offsets scan's tile of 1024 segments, S = N * (C - 1) = 1023, 1024, 1025 and 1040; few rows per image and a low pass
+    # rate leave many segments empty
+    "s1023_c94_n11": dict(seed=13, C=94, rows=[[1 + i % 4] for i in range(11)], frames=_frames(11, 1), flips=[0], pass_rate=0.3),
+    "s1024_c65_n16": dict(seed=14, C=65, rows=[[1 + i % 3] for i in range(16)], frames=_frames(16, 1), flips=[1], pass_rate=0.3),
+    "s1025_c42_n25": dict(seed=15, C=42, rows=[[i % 3] for i in range(25)], frames=_frames(25, 1), flips=[0], pass_rate=0.3),
+    "s1040_c81_n13": dict(seed=16, C=81, rows=[[2, i % 2] for i in range(13)], frames=_frames(13, 2), flips=[0, 1], pass_rate=0.2),
+    # a segment of 68 count slots (17 tiles of 128 rows, 4 waves each): the prefix scan's tile of 64 slots and its carry
+    "c3_68_slots": dict(seed=17, C=3, rows=[[2100, 5]], frames=_frames(1, 2), flips=[0, 1], pass_rate=0.3),
 }
 
 

@@ -108,6 +108,25 @@ def test_chunk_boundaries_inside_masks_and_mask_boundaries_inside_chunks():
     _check([_runs(rng, CHUNK)] + [_runs(rng, CHUNK)])          # masks that are exactly a chunk
 
 
+@pytest.mark.parametrize("total", [1, CHUNK - 1, CHUNK, CHUNK + 1])
+def test_total_runs_around_one_chunk(total):
+    """one chunk, not quite full and full, and one chunk plus one run; masks without runs in front, inside and behind"""
+    rng = np.random.RandomState(total)
+    runs = _runs(rng, total)
+    _check([runs])
+    cut = total // 2
+    _check([[], runs[:cut], [], [], runs[cut:], []], shifts=(0, 7))
+
+
+def test_more_chunks_than_the_offsets_scan_has_threads():
+    """257 chunks: the scan over the chunks' bytes carries across its tile of 256; masks without runs at the start, at a chunk
+    boundary (the tile's boundary among them) and at the end"""
+    rng = np.random.RandomState(8)
+    masks = [[], [], _runs(rng, 100 * CHUNK), [], _runs(rng, 156 * CHUNK), [], [], _runs(rng, CHUNK - 5), [1, 2, 3, 4, 5], [], []]
+    assert sum(len(m) for m in masks) == 257 * CHUNK
+    _check(masks)
+
+
 def test_an_interior_mask_of_many_runs_between_tiny_ones():
     rng = np.random.RandomState(3)
     _check([[1], [2, 3], _runs(rng, 5 * CHUNK + 77), [4], [], [5, 6, 7]], shifts=(0, 9))

@@ -174,6 +174,33 @@ def test_rle_decodes_to_the_dense_planes_exactly(name):
         assert misses > 0, "no box off the image in this case"
 
 
+@pytest.mark.parametrize("W", [63, 64, 65, 129])
+@pytest.mark.parametrize("N", [1, 64, 65])
+def test_rle_across_the_scan_tiles_of_64_columns_and_64_detections(N, W):
+    """the scan over a detection's columns runs in tiles of 64 columns of the widest image, the scan over the detections'
+    run counts in tiles of 64 detections: widths and batch sizes on both sides of a tile, on tiny maps (M = 4, padding 1).
+    From 8 detections on the batch holds boxes off the image (no foreground: one run) and boxes larger than it (a window of
+    the full height, whose columns chain).  The runs decode to the dense kernel's planes exactly, and those are the torch
+    path's outside its near pixels."""
+    H = 21
+    case = _random_case(1000 + 10 * N + W, 4, [(H, W, N)])
+    args = (case["maps"].to(DEV), case["boxes"].to(DEV), case["sizes"], case["threshold"], case["padding"])
+    _, views = _C().paste_masks(*args, counts=case["counts"])
+    counts, run_offset = _C().paste_masks_rle(*args, counts=case["counts"])
+    windows = _windows(case["boxes"], case["M"], case["padding"], case["det_sizes"])
+    _check_case(views, case["planes"], case["near"], windows)
+    assert tuple(run_offset.shape) == (N + 1,) and int(run_offset[0]) == 0 and int(run_offset[-1]) == counts.numel()
+    rles = _rle_dicts(counts, run_offset, case["det_sizes"])
+    for rle, plane in zip(rles, views[0][:, 0].cpu()):
+        mcpu.assert_canonical(rle)
+        assert torch.equal(mcpu.rle_decode(rle), plane)
+    assert any(len(r["counts"]) > 1 for r in rles)
+    if N >= 8:
+        assert any(r["counts"] == [H * W] for r in rles), "no detection without foreground"
+        assert any(y_lo == 0 and y_hi == H and len(r["counts"]) > 1 for r, (_, _, y_lo, y_hi) in zip(rles, windows)), \
+            "no window of the full height"
+
+
 def test_rle_special_planes():
     """pixel (0, 0) set (first count 0), a full-height window whose columns chain, an all-ones plane"""
     maps = torch.ones(3, 1, 14, 14, device=DEV)

@@ -549,7 +549,7 @@ def test_nms_edge_cases():
 def test_nms_dependency_chains(step, thr):
     """boxes marching along x with descending scores: the greedy choice is a dependency chain through every row
     block (worst case of the one-wave scan's fixed-point resolve); n = 4097 takes the shared-memory scan."""
-    for n in (64, 200, 2000, 4096, 4097):
+    for n in (64, 200, 2000, 4095, 4096, 4097):
         x0 = np.arange(n, dtype=np.float32) * step
         b = np.stack([x0, np.zeros(n, np.float32), x0 + 99, np.full(n, 49, np.float32)], 1)
         sc = np.linspace(1.0, 0.1, n).astype(np.float32)

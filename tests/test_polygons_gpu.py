@@ -119,6 +119,37 @@ def test_targets_of_large_instances_and_extreme_boxes(big_reference):
     assert not bad, bad
 
 
+def edge_chunk_shapes():
+    """a 200-pixel image with polygons of 3, 255, 256 and 257 edges (a chunk of 256 staged edges not full, full, and one edge
+    more) and one of 258 whose long sides are 128 collinear vertices each: 254 vertical edges, which cross no column boundary
+    and share their place in the chunk's work list with the next edge that does"""
+    rng = np.random.RandomState(12)
+
+    def gon(k):
+        a = np.arange(k) * (2 * math.pi / k) + 0.1
+        r = 80 + 6 * rng.uniform(-1, 1, k)
+        return np.stack([100.3 + r * np.cos(a), 99.6 + r * np.sin(a)], axis=1).reshape(-1).tolist()
+
+    ys = np.linspace(20.25, 180.5, 128)
+    comb = [v for y in ys for v in (30.5, float(y))] + [100.0, 195.0] + [v for y in ys[::-1] for v in (169.25, float(y))] + [100.0, 5.0]
+    return PolygonList([[gon(3)], [gon(255)], [gon(256)], [gon(257)], [comb]], (200, 200))
+
+
+def test_polygons_around_one_chunk_of_edges_and_mostly_vertical_edges():
+    plist = edge_chunk_shapes()
+    assert [len(inst.polygons[0]) // 2 for inst in plist] == [3, 255, 256, 257, 258]
+    lists = [plist]
+    slots = [(0, g, box) for g in range(5) for box in ((10.2, 8.7, 190.4, 191.1), (60.5, 20.0, 150.25, 120.75))]
+    want = literal_targets(lists, slots, 28)
+    assert all(0.05 < w.mean() < 1 for w in want[::2])
+    assert np.array_equal(device_targets(lists, slots, 28).numpy(), want)
+    H = W = 200
+    planes = np.stack([R.fill_instance([p.tolist() for p in inst.polygons], H, W) for inst in plist])
+    assert all(0 < p.sum() < H * W for p in planes)
+    got = SegmentationMask(plist.to(DEV), (W, H), mode="poly").get_mask_tensor().cpu().numpy()
+    assert np.array_equal(got, planes)
+
+
 def plane_instances(H, W):
     """five instances on an H x W image: a polygon leaving the image on each side, one inside, one with two polygons"""
     return [

@@ -153,6 +153,45 @@ def test_exactly_the_capacity_and_one_row_more():
     _check(got, ref, "rows == capacity - 1, after an overflow")
 
 
+# The compaction ranks the rows among the candidates (every anchor of the pyramid) in rounds of 256 candidates, 4 waves, with
+# a running base: name -> (levels, anchors per location, images, rows).  255 / 256 / 257 candidates are a round not full,
+# full, and a second round of one candidate, on a second level (no candidate at all: test_no_row_at_all_gives_exact_zeros); 255 / 256 / 257 rows
+# of the module's pyramid fill every wave of every round and cross a workgroup's 1024 candidates.
+COMPACTION_CASES = {
+    "candidates-255": ([(15, 17)], 1, 1, 40),
+    "candidates-256": ([(16, 16)], 1, 1, 40),
+    "candidates-257": ([(15, 17), (1, 2)], 1, 1, 40),
+    "rows-255": (LEVELS, A, N, 255),
+    "rows-256": (LEVELS, A, N, 256),
+    "rows-257": (LEVELS, A, N, 257),
+}
+
+
+def compaction_case(name, monkeypatch):
+    """-> (parameters, features, incoming gradients, rows) of a case, this module's pyramid set to the case's; the first and
+    the last candidate are rows"""
+    import sys
+    levels, a, n, rows = COMPACTION_CASES[name]
+    me = sys.modules[__name__]
+    for k, v in (("LEVELS", levels), ("A", a), ("N", n)):
+        monkeypatch.setattr(me, k, v)
+    h, w = levels[-1]
+    first, last = (0, 0, 0, 0, 0), (len(levels) - 1, n - 1, h - 1, w - 1, a - 1)
+    entries = [first] + [e for e in _random_entries(rows, 30 + rows) if e not in (first, last)][:rows - 2] + [last]
+    assert len(entries) == rows
+    p, feats = _head(9)
+    return (p, feats) + tuple(_grads_from_entries(entries)) + (rows,)
+
+
+@pytest.mark.parametrize("case", sorted(COMPACTION_CASES))
+def test_candidates_and_rows_around_one_round_of_the_compaction(case, monkeypatch):
+    p, feats, gobj, gbox, rows = compaction_case(case, monkeypatch)
+    ref, _ = _dense_f64(p, feats, gobj, gbox)
+    got, _, _, _ = _sparse(p, feats, gobj, gbox, max_rows=rows)         # exactly the capacity: one row more would overflow
+    _check(got, ref, case)
+    assert _C.rpn_sparse_overflows() == 0
+
+
 def test_relu_mask_follows_bias_act_rule_for_nan_and_zero_activations():
     """m = 0 where t <= 0, 1 otherwise: a dead pixel takes no gradient (not even a NaN one)"""
     p, feats = _head(6)

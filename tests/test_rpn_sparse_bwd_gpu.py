@@ -124,6 +124,23 @@ def test_headline_shapes_sparse_equals_the_dense_library_path(monkeypatch):
     assert _C.rpn_sparse_overflows() == 0
 
 
+@pytest.mark.parametrize("case", ["candidates-255", "candidates-256", "candidates-257", "rows-255", "rows-256", "rows-257"])
+def test_candidates_and_rows_around_one_round_of_the_compaction(case, monkeypatch):
+    """the cases of tests/test_rpn_sparse_bwd_emu.py (its helpers, its fp64 reference) on the device"""
+    import test_rpn_sparse_bwd_emu as E
+    from maskrcnn_benchmark import _C
+    monkeypatch.setattr(torch.backends.cudnn, "allow_tf32", False)
+    assert case in E.COMPACTION_CASES
+    p, feats, gobj, gbox, rows = E.compaction_case(case, monkeypatch)
+    ref, _ = E._dense_f64(p, feats, gobj, gbox)
+    _C.rpn_sparse_overflows(reset=True)
+    got, _, _, _ = E._sparse({k: v.cuda() for k, v in p.items()}, [f.cuda() for f in feats], [g.cuda() for g in gobj],
+                             [g.cuda() for g in gbox], max_rows=rows)
+    torch.cuda.synchronize()
+    E._check({k: v.cpu() for k, v in got.items()}, ref, case)
+    assert _C.rpn_sparse_overflows() == 0
+
+
 def test_reduced_shape_equals_fp64_autograd_on_the_cpu(monkeypatch):
     from maskrcnn_benchmark import _C
     monkeypatch.setattr(torch.backends.cudnn, "allow_tf32", False)
