@@ -10,6 +10,24 @@
 // mask) once, computes the 4 tap indices + weights once, and then walks a chunk of channels.
 // Lanes run along wo, so offset loads, column stores/loads and gradient stores are coalesced and
 // the 4 gathers of neighbouring lanes fall into neighbouring addresses.
+//
+// Steps that more than one kernel takes are written once.  None of them returns early, holds a barrier (transpose_tile
+// excepted) or uses a wave-wide operation, so a partial wave may call them, and a kernel that keeps dead lanes alive —
+// the ELL gather and ell_build_kernel for __ballot, coord_nhwc_kernel for __shfl — calls them with those lanes pointed
+// at a valid element.  Floating-point expressions stay whole statements inside them (the build fuses within a statement
+// only): a helper hands out operands, the product-sums stay where they were.
+//   point_sample(q, g, img, offset)       offsets -> sampling position -> Sample; img = group_image(g, b, dgi)
+//   point_mask(mask, g, img, tap, pix)    the modulation, 1 when mask is null
+//   chan_range(g, by, cchunk)             deformable group and channel range of workgroup row `by`
+//   point_taps(q, s, m, g)                corner pixels, weights * m (one product each), column index of the point
+//   gather_block / gather_launch_shape    block order and grid of the two pixel-owner gathers (CSR, ELL)
+//   ell_index(ws, P) / ell_build<T>       the fixed-width index inside a workspace; clear + fill under either build
+//   ell_record / ell_sort8 / ell_spill    a pixel's 64-byte record as (point, weight) x 8; the 8-slot sort; overflow append
+//   ell_overflow_point / ell_overflow_add_pairs   overflow entry -> (tap, point); the packed-atomic tail (a grid-stride loop)
+//   atomic_add_t / atomic_add2_t          one element (16-bit types: compare-and-swap on the dword) / an aligned pair
+//   transpose_tile<U>                     32 channels x 64 pixels NCHW -> NHWC through LDS: ALL kBlock threads, one barrier
+//   vec_load / vec_store                  16 bytes of channels <-> fp32 registers (Vec<T, max_vec<T>()> and Io<T>)
+//   nhwc_launch_map<T> / nhwc_grid        the gate and the grid of the four channels-last launchers
 #include <cstdlib>
 
 #include "detops_devlib.h"
@@ -22,32 +40,30 @@ constexpr int kBlock = 256;
 template <typename T> __device__ __forceinline__ float ld(const T* p) { return Io<T>::ld(*p); }
 template <typename T> __device__ __forceinline__ void st(T* p, float v) { *p = Io<T>::st(v); }
 
-__device__ __forceinline__ void atomic_add_t(float* p, float v) { atomicAdd(p, v); }
-__device__ __forceinline__ void atomic_add_t(__half* p, float v) {
-  // 16-bit atomics: CAS on the containing dword
-  unsigned* base = reinterpret_cast<unsigned*>(reinterpret_cast<uintptr_t>(p) & ~uintptr_t(3));
-  const bool hi = reinterpret_cast<uintptr_t>(p) & 2;
-  unsigned old = *base, assumed;
-  do {
-    assumed = old;
-    const unsigned short cur = hi ? (assumed >> 16) : (assumed & 0xffffu);
-    const __half nh = __float2half(__half2float(__ushort_as_half(cur)) + v);
-    const unsigned short nb = __half_as_ushort(nh);
-    const unsigned repl = hi ? ((assumed & 0xffffu) | (static_cast<unsigned>(nb) << 16))
-                             : ((assumed & 0xffff0000u) | nb);
-    old = atomicCAS(base, assumed, repl);
-  } while (old != assumed);
+// a 16-bit storage value <-> its bit pattern (registers only: the copies are folded away)
+template <typename T> __device__ __forceinline__ T from_bits16(unsigned short u) {
+  static_assert(sizeof(T) == 2, "16-bit storage types");
+  T t;
+  __builtin_memcpy(&t, &u, 2);
+  return t;
 }
-__device__ __forceinline__ void atomic_add_t(__hip_bfloat16* p, float v) {
+template <typename T> __device__ __forceinline__ unsigned short bits16(T t) {
+  static_assert(sizeof(T) == 2, "16-bit storage types");
+  unsigned short u;
+  __builtin_memcpy(&u, &t, 2);
+  return u;
+}
+
+__device__ __forceinline__ void atomic_add_t(float* p, float v) { atomicAdd(p, v); }
+// 16-bit atomics: CAS on the containing dword
+template <typename T> __device__ __forceinline__ void atomic_add_t(T* p, float v) {
   unsigned* base = reinterpret_cast<unsigned*>(reinterpret_cast<uintptr_t>(p) & ~uintptr_t(3));
   const bool hi = reinterpret_cast<uintptr_t>(p) & 2;
   unsigned old = *base, assumed;
   do {
     assumed = old;
     const unsigned short cur = hi ? (assumed >> 16) : (assumed & 0xffffu);
-    const float f = __uint_as_float(static_cast<unsigned>(cur) << 16) + v;
-    const __hip_bfloat16 nbf = __float2bfloat16(f);
-    const unsigned short nb = *reinterpret_cast<const unsigned short*>(&nbf);
+    const unsigned short nb = bits16(Io<T>::st(Io<T>::ld(from_bits16<T>(cur)) + v));
     const unsigned repl = hi ? ((assumed & 0xffffu) | (static_cast<unsigned>(nb) << 16))
                              : ((assumed & 0xffff0000u) | nb);
     old = atomicCAS(base, assumed, repl);
@@ -110,18 +126,53 @@ __device__ __forceinline__ Point decode(int64_t p, const Geom& g) {
   return q;
 }
 
+// ---- the sampling-point preamble, shared by every kernel of the file.  `img` = b * deformable_group + dgi names the
+// offset / mask plane set of a sampling point (the channels-last kernels, deformable_group == 1, pass b).
+__device__ __forceinline__ size_t group_image(const Geom& g, int b, int dgi) { return static_cast<size_t>(b) * g.dg + dgi; }
+
 template <typename T>
-__device__ __forceinline__ Sample point_sample(const Point& q, const Geom& g, int dgi,
-                                               const T* __restrict__ offset) {
+__device__ __forceinline__ Sample point_sample(const Point& q, const Geom& g, size_t img, const T* __restrict__ offset) {
   const int K = g.kh * g.kw;
   const int i = q.tap / g.kw, j = q.tap - i * g.kw;
   const size_t HWo = static_cast<size_t>(g.Ho) * g.Wo;
-  const T* op = offset + (static_cast<size_t>(q.b) * g.dg + dgi) * 2 * K * HWo;
+  const T* op = offset + img * 2 * K * HWo;
   const float off_h = ld(op + (2 * q.tap) * HWo + q.pix);
   const float off_w = ld(op + (2 * q.tap + 1) * HWo + q.pix);
   const float h_im = static_cast<float>(q.ho * g.stride_h - g.pad_h + i * g.dil_h) + off_h;
   const float w_im = static_cast<float>(q.wo * g.stride_w - g.pad_w + j * g.dil_w) + off_w;
   return make_sample(h_im, w_im, g.H, g.W);
+}
+
+// the modulation of a sampling point: 1 without a mask (v1)
+template <typename T>
+__device__ __forceinline__ float point_mask(const T* __restrict__ mask, const Geom& g, size_t img, int tap, int pix) {
+  const size_t HWo = static_cast<size_t>(g.Ho) * g.Wo;
+  return mask ? ld(mask + (img * (g.kh * g.kw) + tap) * HWo + pix) : 1.f;
+}
+
+// the channels [c0, c1) of deformable group dgi that workgroup row `by` walks: grid.y = dg * ceil(C / dg / cchunk)
+struct ChanRange { int dgi, c0, c1; };
+__device__ __forceinline__ ChanRange chan_range(const Geom& g, int by, int cchunk) {
+  const int cpg = g.C / g.dg;
+  const int chunks_per_g = (cpg + cchunk - 1) / cchunk;
+  ChanRange r;
+  r.dgi = by / chunks_per_g;
+  r.c0 = r.dgi * cpg + (by - r.dgi * chunks_per_g) * cchunk;
+  r.c1 = min(r.c0 + cchunk, (r.dgi + 1) * cpg);
+  return r;
+}
+
+// what a sampling point hands to an inverted index or a channel-fastest gather: its four corner pixels (flat index, -1
+// outside the map), their bilinear weights times the modulation m, and the point's offset inside one channel's K rows
+// of the column matrix
+struct PointTaps {
+  int tgt[4];
+  float wgt[4];
+  int32_t colidx;    // tap * B * Ho * Wo + b * Ho * Wo + pix
+};
+__device__ __forceinline__ PointTaps point_taps(const Point& q, const Sample& s, float m, const Geom& g) {
+  const int HWo = g.Ho * g.Wo;
+  return PointTaps{{s.i1, s.i2, s.i3, s.i4}, {s.w1 * m, s.w2 * m, s.w3 * m, s.w4 * m}, q.tap * (g.B * HWo) + q.b * HWo + q.pix};
 }
 
 // ------------------------------------------------------------------------------------ im2col
@@ -132,17 +183,12 @@ im2col_kernel(const T* __restrict__ im, const T* __restrict__ offset, const T* _
               T* __restrict__ col, Geom g, int cchunk, int64_t npoints) {
   const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (p >= npoints) return;
-  const int cpg = g.C / g.dg;
-  const int chunks_per_g = (cpg + cchunk - 1) / cchunk;
-  const int dgi = blockIdx.y / chunks_per_g;
-  const int c0 = dgi * cpg + (blockIdx.y - dgi * chunks_per_g) * cchunk;
-  const int c1 = min(c0 + cchunk, (dgi + 1) * cpg);
+  const auto [dgi, c0, c1] = chan_range(g, blockIdx.y, cchunk);
   const Point q = decode(p, g);
   const int K = g.kh * g.kw;
-  const Sample s = point_sample(q, g, dgi, offset);
-  float m = 1.f;
-  if (mask)
-    m = ld(mask + ((static_cast<size_t>(q.b) * g.dg + dgi) * K + q.tap) * g.Ho * g.Wo + q.pix);
+  const size_t img = group_image(g, q.b, dgi);
+  const Sample s = point_sample(q, g, img, offset);
+  const float m = point_mask(mask, g, img, q.tap, q.pix);
   const size_t plane = static_cast<size_t>(g.H) * g.W;
   const size_t ncol = static_cast<size_t>(g.B) * g.Ho * g.Wo;
   const T* ip = im + (static_cast<size_t>(q.b) * g.C + c0) * plane;
@@ -181,18 +227,13 @@ col2im_kernel(const T* __restrict__ col, const T* __restrict__ offset, const T* 
               T* __restrict__ grad_im, Geom g, int cchunk, int64_t npoints) {
   const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (p >= npoints) return;
-  const int cpg = g.C / g.dg;
-  const int chunks_per_g = (cpg + cchunk - 1) / cchunk;
-  const int dgi = blockIdx.y / chunks_per_g;
-  const int c0 = dgi * cpg + (blockIdx.y - dgi * chunks_per_g) * cchunk;
-  const int c1 = min(c0 + cchunk, (dgi + 1) * cpg);
+  const auto [dgi, c0, c1] = chan_range(g, blockIdx.y, cchunk);
   const Point q = decode(p, g);
   const int K = g.kh * g.kw;
-  const Sample s = point_sample(q, g, dgi, offset);
+  const size_t img = group_image(g, q.b, dgi);
+  const Sample s = point_sample(q, g, img, offset);
   if (!s.inside) return;  // get_gradient_weight returns 0 outside (:127-131)
-  float m = 1.f;
-  if (mask)
-    m = ld(mask + ((static_cast<size_t>(q.b) * g.dg + dgi) * K + q.tap) * g.Ho * g.Wo + q.pix);
+  const float m = point_mask(mask, g, img, q.tap, q.pix);
   const size_t plane = static_cast<size_t>(g.H) * g.W;
   const size_t ncol = static_cast<size_t>(g.B) * g.Ho * g.Wo;
   T* gp = grad_im + (static_cast<size_t>(q.b) * g.C + c0) * plane;
@@ -232,11 +273,7 @@ col2im_tile_kernel(const T* __restrict__ col, const T* __restrict__ offset, cons
   const int tix = t % tiles_x; t /= tiles_x;
   const int tiy = t % tiles_y;
   const int b = t / tiles_y;
-  const int cpg = g.C / g.dg;
-  const int chunks_per_g = (cpg + cchunk - 1) / cchunk;
-  const int dgi = blockIdx.y / chunks_per_g;
-  const int c0 = dgi * cpg + (blockIdx.y - dgi * chunks_per_g) * cchunk;
-  const int c1 = min(c0 + cchunk, (dgi + 1) * cpg);
+  const auto [dgi, c0, c1] = chan_range(g, blockIdx.y, cchunk);
   const int ho = tiy * kColTY + tid / kColTX;
   const int wo = tix * kColTX + (tid & (kColTX - 1));
   const bool live = ho < g.Ho && wo < g.Wo;
@@ -249,8 +286,7 @@ col2im_tile_kernel(const T* __restrict__ col, const T* __restrict__ offset, cons
   const int ry0 = tiy * kColTY * g.stride_h - g.pad_h - kColHalo;
   const int rx0 = tix * kColTX * g.stride_w - g.pad_w - kColHalo;
   const int rarea = RH * RW;
-  const T* op = offset + (static_cast<size_t>(b) * g.dg + dgi) * 2 * K * HWo;
-  const T* mp = mask ? mask + (static_cast<size_t>(b) * g.dg + dgi) * K * HWo : nullptr;
+  const size_t img = group_image(g, b, dgi);
 
   for (int cs = c0; cs < c1; cs += CC) {
     const int cn = min(CC, c1 - cs);
@@ -259,14 +295,10 @@ col2im_tile_kernel(const T* __restrict__ col, const T* __restrict__ offset, cons
     if (live) {
       T* gp0 = grad_im + (static_cast<size_t>(b) * g.C + cs) * plane;
       for (int tap = 0; tap < K; ++tap) {
-        const int i = tap / g.kw, j = tap - i * g.kw;
-        const float h_im = static_cast<float>(ho * g.stride_h - g.pad_h + i * g.dil_h) + ld(op + (2 * tap) * HWo + pix);
-        const float w_im = static_cast<float>(wo * g.stride_w - g.pad_w + j * g.dil_w) + ld(op + (2 * tap + 1) * HWo + pix);
-        const Sample s = make_sample(h_im, w_im, g.H, g.W);
+        const Sample s = point_sample(Point{b, tap, ho, wo, pix}, g, img, offset);
         if (!s.inside) continue;  // get_gradient_weight returns 0 outside (:127-131)
-        const float m = mp ? ld(mp + tap * HWo + pix) : 1.f;
-        const int h_low = static_cast<int>(floorf(h_im)), w_low = static_cast<int>(floorf(w_im));
-        const int ly = h_low - ry0, lx = w_low - rx0;
+        const float m = point_mask(mask, g, img, tap, pix);
+        const int ly = s.hl - ry0, lx = s.wl - rx0;
         const bool in_win = ly >= 0 && ly + 1 < RH && lx >= 0 && lx + 1 < RW;
         const int wbase = ly * RW + lx;
         const T* cp = col + (static_cast<size_t>(cs) * K + tap) * ncol + static_cast<size_t>(b) * HWo + pix;
@@ -349,21 +381,17 @@ col2im_index_kernel(const T* __restrict__ offset, const T* __restrict__ mask, Ge
   const int dgi = blockIdx.y;
   const Point q = decode(p, g);
   const int K = g.kh * g.kw;
-  const Sample s = point_sample(q, g, dgi, offset);
+  const size_t img = group_image(g, q.b, dgi);
+  const Sample s = point_sample(q, g, img, offset);
   if (!s.inside) return;
-  const int HWo = g.Ho * g.Wo;
-  const size_t base = static_cast<size_t>(q.b * g.dg + dgi) * g.H * g.W;
-  const int tgt[4] = {s.i1, s.i2, s.i3, s.i4};
-  const float wgt[4] = {s.w1, s.w2, s.w3, s.w4};
-  float m = 1.f;
-  if (FILL && mask) m = ld(mask + ((static_cast<size_t>(q.b) * g.dg + dgi) * K + q.tap) * HWo + q.pix);
-  const int32_t colidx = q.tap * (g.B * HWo) + q.b * HWo + q.pix;
+  const size_t base = img * g.H * g.W;
+  const PointTaps pt = point_taps(q, s, FILL ? point_mask(mask, g, img, q.tap, q.pix) : 1.f, g);
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    if (tgt[t] < 0) continue;
-    const size_t slot = (base + tgt[t]) * K + q.tap;
+    if (pt.tgt[t] < 0) continue;
+    const size_t slot = (base + pt.tgt[t]) * K + q.tap;
     const int pos = atomicAdd(counter + slot, 1);  // count pass: the tally; fill pass: the claimed slot
-    if (FILL) entries[start[slot] + pos] = ColEntry{colidx, wgt[t] * m};
+    if (FILL) entries[start[slot] + pos] = ColEntry{pt.colidx, pt.wgt[t]};
   }
 }
 
@@ -384,30 +412,44 @@ col2im_sort_kernel(const int32_t* __restrict__ start, int64_t nslots, ColEntry* 
 
 constexpr int kGatherCC = 16;  // channels per thread pass (independent loads in flight)
 
+// The two pixel-owner gathers (CSR and ELL) share their grid: (pixel block, channel chunk, image), with `cc` channels
+// per workgroup: whole passes of kGatherCC, enough workgroups to fill the chip.
+inline dim3 gather_launch_shape(const Geom& g, int& cc) {
+  const int cpg = g.C / g.dg;
+  const int64_t pix_blocks = ceil_div64(static_cast<int64_t>(g.H) * g.W, kBlock) * g.B;
+  cc = cpg;
+  while (cc > kGatherCC && pix_blocks * g.dg * ceil_div64(cpg, cc) < 4 * kNumCU) cc = max(kGatherCC, cc / 2);
+  cc = static_cast<int>(ceil_div64(cc, kGatherCC)) * kGatherCC;
+  return dim3(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(g.H) * g.W, kBlock)),
+              static_cast<unsigned>(g.dg * ceil_div64(cpg, cc)), static_cast<unsigned>(g.B));
+}
+inline int gather_xcd_remap() { return detops_tuning().dcn_gather_xcd != 1; }   // 1: plain block order (A/B measurements)
+
+// (pixel block, channel chunk, image) from the linear workgroup id; with xcd_remap every XCD owns a contiguous run of
+// pixel blocks of one chunk, so the overlapping column windows of neighbouring pixel blocks are fetched into ONE L2
+// instead of all eight
+__device__ __forceinline__ void gather_block(int& bx, int& by, int& b, int xcd_remap) {
+  int64_t lin = (static_cast<int64_t>(blockIdx.z) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (xcd_remap) lin = xcd_contiguous(lin, static_cast<int64_t>(gridDim.x) * gridDim.y * gridDim.z);
+  bx = static_cast<int>(lin % gridDim.x);
+  by = static_cast<int>((lin / gridDim.x) % gridDim.y);
+  b = static_cast<int>(lin / (static_cast<int64_t>(gridDim.x) * gridDim.y));
+}
+
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
 col2im_gather_kernel(const T* __restrict__ col, const int32_t* __restrict__ start,
                      const ColEntry* __restrict__ entries, T* __restrict__ grad_im, Geom g, int cchunk,
                      int xcd_remap) {
   const int HW = g.H * g.W;
-  // (pixel block, channel chunk, image) from the linear workgroup id; with xcd_remap every XCD owns
-  // a contiguous run of pixel blocks of one chunk, so the overlapping column windows of
-  // neighbouring pixel blocks are fetched into ONE L2 instead of all eight
-  int64_t lin = (static_cast<int64_t>(blockIdx.z) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  if (xcd_remap) lin = xcd_contiguous(lin, static_cast<int64_t>(gridDim.x) * gridDim.y * gridDim.z);
-  const int bx = static_cast<int>(lin % gridDim.x);
-  const int by = static_cast<int>((lin / gridDim.x) % gridDim.y);
-  const int b = static_cast<int>(lin / (static_cast<int64_t>(gridDim.x) * gridDim.y));
+  int bx, by, b;
+  gather_block(bx, by, b, xcd_remap);
   const int pix = bx * kBlock + threadIdx.x;   // pixel within the image plane
   if (pix >= HW) return;
-  const int cpg = g.C / g.dg;
-  const int chunks_per_g = (cpg + cchunk - 1) / cchunk;
-  const int dgi = by / chunks_per_g;
-  const int c0 = dgi * cpg + (by - dgi * chunks_per_g) * cchunk;
-  const int c1 = min(c0 + cchunk, (dgi + 1) * cpg);
+  const auto [dgi, c0, c1] = chan_range(g, by, cchunk);
   const int K = g.kh * g.kw;
   const size_t chan_stride = static_cast<size_t>(K) * g.B * g.Ho * g.Wo;   // one channel's K rows of col
-  const size_t li = (static_cast<size_t>(b) * g.dg + dgi) * HW + pix;
+  const size_t li = group_image(g, b, dgi) * HW + pix;
   const int s0 = start[li * K], s1 = start[li * K + K];
   for (int cs = c0; cs < c1; cs += kGatherCC) {
     float acc[kGatherCC];
@@ -448,10 +490,10 @@ col2im_coord_kernel(const T* __restrict__ col, const T* __restrict__ im, const T
   const int cpg = g.C / g.dg;
   const Point q = decode(live ? p : 0, g);
   const int K = g.kh * g.kw;
-  const Sample s = point_sample(q, g, dgi, offset);
+  const size_t img = group_image(g, q.b, dgi);
+  const Sample s = point_sample(q, g, img, offset);
   const size_t HWo = static_cast<size_t>(g.Ho) * g.Wo;
-  float m = 1.f;
-  if (mask) m = ld(mask + ((static_cast<size_t>(q.b) * g.dg + dgi) * K + q.tap) * HWo + q.pix);
+  const float m = point_mask(mask, g, img, q.tap, q.pix);
   float gh = 0.f, gw = 0.f, gm = 0.f;
   if (live && s.inside) {
     const size_t plane = static_cast<size_t>(g.H) * g.W;
@@ -501,11 +543,10 @@ col2im_coord_kernel(const T* __restrict__ col, const T* __restrict__ im, const T
     }
   }
   if (!live || slice != 0) return;
-  T* gop = grad_offset + (static_cast<size_t>(q.b) * g.dg + dgi) * 2 * K * HWo;
+  T* gop = grad_offset + img * 2 * K * HWo;
   st(gop + (2 * q.tap) * HWo + q.pix, gh);
   st(gop + (2 * q.tap + 1) * HWo + q.pix, gw);
-  if (mask && grad_mask)
-    st(grad_mask + ((static_cast<size_t>(q.b) * g.dg + dgi) * K + q.tap) * HWo + q.pix, gm);
+  if (mask && grad_mask) st(grad_mask + (img * K + q.tap) * HWo + q.pix, gm);
 }
 
 inline int make_geom(Geom& g, int B, int C, int H, int W, int kh, int kw, int pad_h, int pad_w,
@@ -600,6 +641,50 @@ struct EllOverflow {
 
 __device__ __forceinline__ int slot_fetch_add(int32_t* p) { return detops_fetch_add_relaxed(p, 1); }
 
+// one more contribution for the overflow list (li = img * H * W + pixel); entries past its capacity are dropped
+__device__ __forceinline__ void ell_spill(int32_t* ovf_count, EllOverflow* ovf, int ovf_cap, size_t li, int32_t colidx, float w) {
+  const int o = atomicAdd(ovf_count, 1);
+  if (o < ovf_cap) ovf[o] = EllOverflow{static_cast<int32_t>(li), colidx, w};
+}
+
+// the sampling point behind an overflow entry of a deformable_group == 1 index: colidx = tap * B * Ho * Wo + q
+__device__ __forceinline__ void ell_overflow_point(const EllOverflow& o, const Geom& g, int& tap, int& q) {
+  const int per_tap = g.B * (g.Ho * g.Wo);
+  tap = o.colidx / per_tap;
+  q = o.colidx - tap * per_tap;
+}
+
+// the eight (column index, weight) slots of one (pixel, tap) by ascending column index: odd-even transposition sort on
+// registers (static indices).  Unused slots carry the key 0x7fffffff and stay behind.
+__device__ __forceinline__ void ell_sort8(int32_t (&k)[kEllCap], float (&w)[kEllCap]) {
+#pragma unroll
+  for (int r = 0; r < kEllCap; ++r) {
+#pragma unroll
+    for (int j = (r & 1); j + 1 < kEllCap; j += 2) {
+      const bool sw = k[j] > k[j + 1];
+      const int32_t ka = sw ? k[j + 1] : k[j], kb = sw ? k[j] : k[j + 1];
+      const float wa = sw ? w[j + 1] : w[j], wb = sw ? w[j] : w[j + 1];
+      k[j] = ka; k[j + 1] = kb; w[j] = wa; w[j + 1] = wb;
+    }
+  }
+}
+
+// A pixel's whole 64-byte record of one tap in four 16-byte loads (same addresses across the pixel's lane group), as
+// sampling points qi = column index - tap_base (= b * Ho * Wo + pix) and weights wi.  Slots >= n may hold anything (the
+// scatter build leaves them unwritten): they come back as point 0 with weight 0.
+__device__ __forceinline__ void ell_record(const EllEntry* __restrict__ rec, int n, int tap_base, int32_t (&qi)[kEllCap],
+                                           float (&wi)[kEllCap]) {
+  const float4* r4 = reinterpret_cast<const float4*>(rec);
+#pragma unroll
+  for (int j = 0; j < kEllCap; j += 2) {
+    const float4 r = r4[j / 2];
+    qi[j] = (j < n ? __float_as_int(r.x) : tap_base) - tap_base;
+    wi[j] = j < n ? r.y : 0.f;
+    qi[j + 1] = (j + 1 < n ? __float_as_int(r.z) : tap_base) - tap_base;
+    wi[j + 1] = j + 1 < n ? r.w : 0.f;
+  }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
 col2im_ell_fill_kernel(const T* __restrict__ offset, const T* __restrict__ mask, Geom g, int64_t npoints,
@@ -610,32 +695,27 @@ col2im_ell_fill_kernel(const T* __restrict__ offset, const T* __restrict__ mask,
   const int dgi = blockIdx.y;
   const Point q = decode(p, g);
   const int K = g.kh * g.kw;
-  const Sample s = point_sample(q, g, dgi, offset);
+  const size_t img = group_image(g, q.b, dgi);
+  const Sample s = point_sample(q, g, img, offset);
   if (!s.inside) return;
-  const int HW = g.H * g.W, HWo = g.Ho * g.Wo;
-  const int tgt[4] = {s.i1, s.i2, s.i3, s.i4};
-  const float wgt[4] = {s.w1, s.w2, s.w3, s.w4};
-  float m = 1.f;
-  if (mask) m = ld(mask + ((static_cast<size_t>(q.b) * g.dg + dgi) * K + q.tap) * HWo + q.pix);
-  const int32_t colidx = q.tap * (g.B * HWo) + q.b * HWo + q.pix;
-  const size_t img = static_cast<size_t>(q.b) * g.dg + dgi;
+  const int HW = g.H * g.W;
+  const PointTaps pt = point_taps(q, s, point_mask(mask, g, img, q.tap, q.pix), g);
   // the four slot requests first (independent relaxed atomics: four round trips in flight instead of one after the
   // other), then the four record stores
   int pos[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     pos[t] = -1;
-    if (tgt[t] >= 0) pos[t] = slot_fetch_add(counter + (img * K + q.tap) * HW + tgt[t]);   // counter: [img][tap][pixel]
+    if (pt.tgt[t] >= 0) pos[t] = slot_fetch_add(counter + (img * K + q.tap) * HW + pt.tgt[t]);   // counter: [img][tap][pixel]
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    if (tgt[t] < 0) continue;
+    if (pt.tgt[t] < 0) continue;
     if (pos[t] < kEllCap) {
-      const size_t e = ((img * K + q.tap) * HW + tgt[t]) * kEllCap + pos[t];   // [img][tap][pixel][slot]
-      ent[e] = EllEntry{colidx, wgt[t] * m};
+      const size_t e = ((img * K + q.tap) * HW + pt.tgt[t]) * kEllCap + pos[t];   // [img][tap][pixel][slot]
+      ent[e] = EllEntry{pt.colidx, pt.wgt[t]};
     } else {
-      const int o = atomicAdd(ovf_count, 1);
-      if (o < ovf_cap) ovf[o] = EllOverflow{static_cast<int32_t>(img * HW + tgt[t]), colidx, wgt[t] * m};
+      ell_spill(ovf_count, ovf, ovf_cap, img * HW + pt.tgt[t], pt.colidx, pt.wgt[t]);
     }
   }
 }
@@ -658,17 +738,7 @@ col2im_ell_sort_kernel(const int32_t* __restrict__ counter, int64_t ncols, int H
     k[j] = r.idx;
     w[j] = r.w;
   }
-  // odd-even transposition sort on 8 registers (static indices)
-#pragma unroll
-  for (int r = 0; r < kEllCap; ++r) {
-#pragma unroll
-    for (int j = (r & 1); j + 1 < kEllCap; j += 2) {
-      const bool sw = k[j] > k[j + 1];
-      const int32_t ka = sw ? k[j + 1] : k[j], kb = sw ? k[j] : k[j + 1];
-      const float wa = sw ? w[j + 1] : w[j], wb = sw ? w[j] : w[j + 1];
-      k[j] = ka; k[j + 1] = kb; w[j] = wa; w[j + 1] = wb;
-    }
-  }
+  ell_sort8(k, w);
 #pragma unroll
   for (int j = 0; j < kEllCap; ++j)
     if (j < n) ee[j] = EllEntry{k[j], w[j]};
@@ -679,21 +749,14 @@ __global__ void __launch_bounds__(kBlock)
 col2im_ell_gather_kernel(const T* __restrict__ col, const int32_t* __restrict__ counter,
                          const EllEntry* __restrict__ ent, T* __restrict__ grad_im, Geom g, int cchunk, int xcd_remap) {
   const int HW = g.H * g.W;
-  int64_t lin = (static_cast<int64_t>(blockIdx.z) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  if (xcd_remap) lin = xcd_contiguous(lin, static_cast<int64_t>(gridDim.x) * gridDim.y * gridDim.z);
-  const int bx = static_cast<int>(lin % gridDim.x);
-  const int by = static_cast<int>((lin / gridDim.x) % gridDim.y);
-  const int b = static_cast<int>(lin / (static_cast<int64_t>(gridDim.x) * gridDim.y));
+  int bx, by, b;
+  gather_block(bx, by, b, xcd_remap);
   const int pix = bx * kBlock + threadIdx.x;
   const bool live = pix < HW;            // dead lanes stay for the wave-wide ballots
-  const int cpg = g.C / g.dg;
-  const int chunks_per_g = (cpg + cchunk - 1) / cchunk;
-  const int dgi = by / chunks_per_g;
-  const int c0 = dgi * cpg + (by - dgi * chunks_per_g) * cchunk;
-  const int c1 = min(c0 + cchunk, (dgi + 1) * cpg);
+  const auto [dgi, c0, c1] = chan_range(g, by, cchunk);
   const int K = g.kh * g.kw;
   const size_t chan_stride = static_cast<size_t>(K) * g.B * g.Ho * g.Wo;
-  const size_t img = static_cast<size_t>(b) * g.dg + dgi;
+  const size_t img = group_image(g, b, dgi);
   const int p = live ? pix : 0;
   for (int cs = c0; cs < c1; cs += kGatherCC) {
     float acc[kGatherCC];
@@ -772,6 +835,19 @@ inline bool ell_plan(const Geom& g, EllPlan& P) {
   return true;
 }
 
+// the four arrays of the index inside a caller's workspace (counters and the overflow counter are adjacent: one clear)
+struct EllIndex {
+  int32_t* count;
+  int32_t* ovf_count;
+  EllEntry* ent;
+  EllOverflow* ovf;
+};
+inline EllIndex ell_index(void* ws, const EllPlan& P) {
+  char* w = static_cast<char*>(ws);
+  return EllIndex{reinterpret_cast<int32_t*>(w + P.off_count), reinterpret_cast<int32_t*>(w + P.off_ovf_count),
+                  reinterpret_cast<EllEntry*>(w + P.off_ent), reinterpret_cast<EllOverflow*>(w + P.off_ovf)};
+}
+
 // ------------------------------------------------------------------------------------ ELL index, tile-owner build
 // The scatter build above asks a global counter for every tap of every sampling point (1.2 M returning atomics on
 // [tap][pixel] counters at the layer2 size), then a second launch sorts the slots.  Here a workgroup OWNS one
@@ -809,10 +885,10 @@ ell_build_kernel(const T* __restrict__ offset, const T* __restrict__ mask, Geom 
   const int th_log2 = th == 8 ? 3 : 4;
   const int ty = static_cast<int>(blockIdx.x) / tiles_x, tx = static_cast<int>(blockIdx.x) - ty * tiles_x;
   const int tap = blockIdx.y;
-  const int img = blockIdx.z, b = img / g.dg, dgi = img - b * g.dg;
+  const int img = blockIdx.z, b = img / g.dg;            // img = b * deformable_group + dgi
   const int y0 = ty * th, x0 = tx * kEllTW;
   const int npx = th * kEllTW;
-  const int K = g.kh * g.kw, HW = g.H * g.W, HWo = g.Ho * g.Wo;
+  const int K = g.kh * g.kw, HW = g.H * g.W;
   for (int l = tid; l < npx; l += nthr) s_cnt[l] = 0;
   __syncthreads();
   const int ky = tap / g.kw, kx = tap - ky * g.kw;
@@ -824,10 +900,7 @@ ell_build_kernel(const T* __restrict__ offset, const T* __restrict__ mask, Geom 
   int ox_hi = (x0 + kEllTW + kEllM >= g.W) ? g.Wo : min(g.Wo, ceil_div_signed(x0 + kEllTW + kEllM + bx_, g.stride_w));
   const int ncx = max(0, ox_hi - ox_lo), ncy = max(0, oy_hi - oy_lo);
   const size_t lbase = static_cast<size_t>(img) * HW;
-  auto spill = [&](int tgt, int32_t colidx, float w) {
-    const int o = atomicAdd(ovf_count, 1);
-    if (o < ovf_cap) ovf[o] = EllOverflow{static_cast<int32_t>(lbase + tgt), colidx, w};
-  };
+  auto spill = [&](int tgt, int32_t colidx, float w) { ell_spill(ovf_count, ovf, ovf_cap, lbase + tgt, colidx, w); };
   // Slot requests are LDS atomics with return: ~500 cycles per wave instruction on this hardware whatever the number of
   // active lanes.  So a wave first COMPACTS the corners that are this tile's own into its private queue (ballot + lane
   // prefix, no atomics) and requests slots 64 lanes dense: a third of the atomic instructions.
@@ -864,13 +937,9 @@ ell_build_kernel(const T* __restrict__ offset, const T* __restrict__ mask, Geom 
     const bool home = zy >= y0 && zy < y0 + th && zx >= x0 && zx < x0 + kEllTW;
     Point q;
     q.b = b; q.tap = tap; q.ho = live ? oy : 0; q.wo = live ? ox : 0; q.pix = q.ho * g.Wo + q.wo;
-    const Sample s = point_sample(q, g, dgi, offset);
+    const Sample s = point_sample(q, g, img, offset);
     live = live && s.inside;
-    float m = 1.f;
-    if (mask) m = ld(mask + ((static_cast<size_t>(b) * g.dg + dgi) * K + tap) * HWo + q.pix);
-    const int32_t colidx = tap * (g.B * HWo) + b * HWo + q.pix;
-    const int tgt[4] = {s.i1, s.i2, s.i3, s.i4};
-    const float wgt[4] = {s.w1 * m, s.w2 * m, s.w3 * m, s.w4 * m};
+    const auto [tgt, wgt, colidx] = point_taps(q, s, point_mask(mask, g, img, tap, q.pix), g);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int cy = s.hl + (t >> 1), cx = s.wl + (t & 1);        // corner coordinates from the sample's floor
@@ -906,18 +975,7 @@ ell_build_kernel(const T* __restrict__ offset, const T* __restrict__ mask, Geom 
       const EllEntry e = j < n ? s_ent[j][l] : EllEntry{0x7fffffff, 0.f};
       k[j] = e.idx; w[j] = e.w;
     }
-    if (n >= 2) {
-#pragma unroll
-      for (int r = 0; r < kEllCap; ++r) {
-#pragma unroll
-        for (int j = (r & 1); j + 1 < kEllCap; j += 2) {
-          const bool sw = k[j] > k[j + 1];
-          const int32_t ka = sw ? k[j + 1] : k[j], kb = sw ? k[j] : k[j + 1];
-          const float wa = sw ? w[j + 1] : w[j], wb = sw ? w[j] : w[j + 1];
-          k[j] = ka; k[j + 1] = kb; w[j] = wa; w[j + 1] = wb;
-        }
-      }
-    }
+    if (n >= 2) ell_sort8(k, w);
     const int pix = py * g.W + px;
     counter[col0 + pix] = cnt;
     // the whole record, used slots or not: four 16-byte stores, every 64-byte sector of the table written in full
@@ -931,18 +989,17 @@ ell_build_kernel(const T* __restrict__ offset, const T* __restrict__ mask, Geom 
 // Builds counters + slots (+ the overflow list) of the inverted index for one call.  `dcn_ell_build` = 1 keeps the
 // scatter build (A/B).
 template <typename T>
-int ell_build(const void* offset, const void* mask, const Geom& g, const EllPlan& P, int32_t* count, int32_t* ovf_count,
-              EllEntry* ent, EllOverflow* ovf, size_t clear_bytes, hipStream_t st_) {
+int ell_build(const void* offset, const void* mask, const Geom& g, const EllPlan& P, const EllIndex& ix, hipStream_t st_) {
   if (detops_tuning().dcn_ell_build == 1) {
-    DETOPS_HIP_TRY(hipMemsetAsync(count, 0, clear_bytes, st_));   // counters + overflow counter
+    DETOPS_HIP_TRY(hipMemsetAsync(ix.count, 0, P.off_ent - P.off_count, st_));   // counters + overflow counter
     const dim3 pgrid(static_cast<unsigned>(ceil_div64(P.npoints_per_dg, kBlock)), static_cast<unsigned>(g.dg));
     hipLaunchKernelGGL(col2im_ell_fill_kernel<T>, pgrid, dim3(kBlock), 0, st_, static_cast<const T*>(offset),
-                       static_cast<const T*>(mask), g, P.npoints_per_dg, count, ent, ovf_count, ovf, P.ovf_cap);
+                       static_cast<const T*>(mask), g, P.npoints_per_dg, ix.count, ix.ent, ix.ovf_count, ix.ovf, P.ovf_cap);
     hipLaunchKernelGGL(col2im_ell_sort_kernel, dim3(static_cast<unsigned>(ceil_div64(P.ncols, kBlock))), dim3(kBlock),
-                       0, st_, static_cast<const int32_t*>(count), P.ncols, g.H * g.W, ent);
+                       0, st_, static_cast<const int32_t*>(ix.count), P.ncols, g.H * g.W, ix.ent);
     return launch_status();
   }
-  DETOPS_HIP_TRY(hipMemsetAsync(ovf_count, 0, sizeof(int32_t), st_));
+  DETOPS_HIP_TRY(hipMemsetAsync(ix.ovf_count, 0, sizeof(int32_t), st_));
   const int K = g.kh * g.kw;
   const int tiles_x = static_cast<int>(ceil_div64(g.W, kEllTW));
   int th = kEllTH;
@@ -953,7 +1010,7 @@ int ell_build(const void* offset, const void* mask, const Geom& g, const EllPlan
   hipLaunchKernelGGL(ell_build_kernel<T>, dim3(static_cast<unsigned>(tiles_x * tiles_y), static_cast<unsigned>(K),
                                                static_cast<unsigned>(g.B * g.dg)),
                      dim3(nthr), 0, st_, static_cast<const T*>(offset), static_cast<const T*>(mask), g, th, tiles_x,
-                     count, ent, ovf_count, ovf, P.ovf_cap);
+                     ix.count, ix.ent, ix.ovf_count, ix.ovf, P.ovf_cap);
   return launch_status();
 }
 
@@ -961,25 +1018,15 @@ template <typename T>
 int col2im_ell_t(const void* col, const void* offset, const void* mask, void* grad_im, const Geom& g,
                  const EllPlan& P, void* ws, hipStream_t st_) {
   if (P.npoints_per_dg == 0) return 0;
-  char* w = static_cast<char*>(ws);
-  int32_t* count = reinterpret_cast<int32_t*>(w + P.off_count);
-  int32_t* ovf_count = reinterpret_cast<int32_t*>(w + P.off_ovf_count);
-  EllEntry* ent = reinterpret_cast<EllEntry*>(w + P.off_ent);
-  EllOverflow* ovf = reinterpret_cast<EllOverflow*>(w + P.off_ovf);
-  { const int rc = ell_build<T>(offset, mask, g, P, count, ovf_count, ent, ovf, P.off_ent - P.off_count, st_); if (rc) return rc; }
-  const int cpg = g.C / g.dg;
-  const int64_t pix_blocks = ceil_div64(static_cast<int64_t>(g.H) * g.W, kBlock) * g.B;
-  int cc = cpg;
-  while (cc > kGatherCC && pix_blocks * g.dg * ceil_div64(cpg, cc) < 4 * kNumCU) cc = max(kGatherCC, cc / 2);
-  cc = static_cast<int>(ceil_div64(cc, kGatherCC)) * kGatherCC;
-  const int xcd_remap = detops_tuning().dcn_gather_xcd != 1;
-  const dim3 ggrid(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(g.H) * g.W, kBlock)),
-                   static_cast<unsigned>(g.dg * ceil_div64(cpg, cc)), static_cast<unsigned>(g.B));
+  const EllIndex ix = ell_index(ws, P);
+  if (const int rc = ell_build<T>(offset, mask, g, P, ix, st_)) return rc;
+  int cc;
+  const dim3 ggrid = gather_launch_shape(g, cc);
   hipLaunchKernelGGL(col2im_ell_gather_kernel<T>, ggrid, dim3(kBlock), 0, st_, static_cast<const T*>(col),
-                     static_cast<const int32_t*>(count), static_cast<const EllEntry*>(ent), static_cast<T*>(grad_im), g, cc,
-                     xcd_remap);
+                     static_cast<const int32_t*>(ix.count), static_cast<const EllEntry*>(ix.ent), static_cast<T*>(grad_im), g, cc,
+                     gather_xcd_remap());
   hipLaunchKernelGGL(col2im_ell_overflow_kernel<T>, dim3(kNumCU), dim3(kBlock), 0, st_, static_cast<const T*>(col),
-                     static_cast<const int32_t*>(ovf_count), static_cast<const EllOverflow*>(ovf), P.ovf_cap,
+                     static_cast<const int32_t*>(ix.ovf_count), static_cast<const EllOverflow*>(ix.ovf), P.ovf_cap,
                      static_cast<T*>(grad_im), g);
   return launch_status();
 }
@@ -1034,17 +1081,11 @@ int col2im_gather_t(const void* col, const void* offset, const void* mask, void*
                      entries);
   hipLaunchKernelGGL(col2im_sort_kernel, dim3(static_cast<unsigned>(ceil_div64(P.nslots, kBlock))), dim3(kBlock), 0,
                      st_, static_cast<const int32_t*>(start), P.nslots, entries);
-  const int cpg = g.C / g.dg;
-  const int64_t pix_blocks = ceil_div64(static_cast<int64_t>(g.H) * g.W, kBlock) * g.B;
-  int cc = cpg;  // channels per workgroup: whole passes of kGatherCC, enough workgroups to fill the chip
-  while (cc > kGatherCC && pix_blocks * g.dg * ceil_div64(cpg, cc) < 4 * kNumCU) cc = max(kGatherCC, cc / 2);
-  cc = static_cast<int>(ceil_div64(cc, kGatherCC)) * kGatherCC;
-  const int xcd_remap = detops_tuning().dcn_gather_xcd != 1;   // 1: plain block order (A/B measurements)
-  const dim3 ggrid(static_cast<unsigned>(ceil_div64(static_cast<int64_t>(g.H) * g.W, kBlock)),
-                   static_cast<unsigned>(g.dg * ceil_div64(cpg, cc)), static_cast<unsigned>(g.B));
+  int cc;
+  const dim3 ggrid = gather_launch_shape(g, cc);
   hipLaunchKernelGGL(col2im_gather_kernel<T>, ggrid, dim3(kBlock), 0, st_, static_cast<const T*>(col),
                      static_cast<const int32_t*>(start), static_cast<const ColEntry*>(entries),
-                     static_cast<T*>(grad_im), g, cc, xcd_remap);
+                     static_cast<T*>(grad_im), g, cc, gather_xcd_remap());
   return launch_status();
 }
 
@@ -1099,29 +1140,43 @@ constexpr int kFK = 32;              // channel granularity of the fused plan ((
 #define DCN_MFMA_F16(a, b, c) DETOPS_MFMA_32x32x16_F16(a, b, c)
 #define DCN_MFMA_BF16(a, b, c) DETOPS_MFMA_32x32x16_BF16(a, b, c)
 
-// pre-pass: blocks [0, nb_im): input NCHW -> NHWC (32 channels x 64 pixels per block through LDS);
-//           the rest: weights [Cout, C, T] -> [T, Cout, C]
+// One 32-channel x 64-pixel tile of [B, C, HW] -> [B, HW, C] through LDS (element size 2 or 4 bytes; the row padding of 4
+// bytes spreads the channel-fastest reads over the banks).  Workgroup `block` of B * ceil(C / 32) * ceil(HW / 64), all
+// kBlock threads (it holds a barrier); ragged tiles are cut at C and HW.
+constexpr int kTrC = 32, kTrP = 64;
+template <typename U> using TransposeTile = U[kTrC][kTrP + 4 / sizeof(U)];
+inline int64_t transpose_blocks(int B, int C, int HW) {
+  return static_cast<int64_t>(B) * ((HW + kTrP - 1) / kTrP) * ((C + kTrC - 1) / kTrC);
+}
+template <typename U>
+__device__ __forceinline__ void transpose_tile(TransposeTile<U>& tile, const U* __restrict__ in, U* __restrict__ out, int C,
+                                               int HW, int block) {
+  const int tid = threadIdx.x;
+  const int pblocks = (HW + kTrP - 1) / kTrP, cblocks = (C + kTrC - 1) / kTrC;
+  int r = block;
+  const int pb = r % pblocks; r /= pblocks;
+  const int cb = r % cblocks;
+  const int b = r / cblocks;
+  const int p0 = pb * kTrP, c0 = cb * kTrC;
+  for (int e = tid; e < kTrC * kTrP; e += kBlock) {   // read: pixels fastest
+    const int c = e / kTrP, pp = e % kTrP;
+    tile[c][pp] = (c0 + c < C && p0 + pp < HW) ? in[(static_cast<size_t>(b) * C + c0 + c) * HW + p0 + pp] : U(0);
+  }
+  __syncthreads();
+  for (int e = tid; e < kTrC * kTrP; e += kBlock) {   // write: channels fastest
+    const int pp = e / kTrC, c = e % kTrC;
+    if (c0 + c < C && p0 + pp < HW) out[(static_cast<size_t>(b) * HW + p0 + pp) * C + c0 + c] = tile[c][pp];
+  }
+}
+
+// pre-pass: blocks [0, nb_im): input NCHW -> NHWC (transpose_tile); the rest: weights [Cout, C, T] -> [T, Cout, C]
 __global__ void __launch_bounds__(kBlock)
 dcn_fused_prep_kernel(const dcn_u16* __restrict__ im, const dcn_u16* __restrict__ w, dcn_u16* __restrict__ imT,
                       dcn_u16* __restrict__ wt, int B, int C, int HW, int Cout, int T, int nb_im) {
-  __shared__ dcn_u16 tile[32][66];
+  __shared__ TransposeTile<dcn_u16> tile;
   const int tid = threadIdx.x;
   if (static_cast<int>(blockIdx.x) < nb_im) {
-    const int pblocks = (HW + 63) / 64, cblocks = (C + 31) / 32;
-    int r = blockIdx.x;
-    const int pb = r % pblocks; r /= pblocks;
-    const int cb = r % cblocks;
-    const int b = r / cblocks;
-    const int p0 = pb * 64, c0 = cb * 32;
-    for (int e = tid; e < 32 * 64; e += kBlock) {   // read: pixels fastest
-      const int c = e >> 6, pp = e & 63;
-      tile[c][pp] = (c0 + c < C && p0 + pp < HW) ? im[(static_cast<size_t>(b) * C + c0 + c) * HW + p0 + pp] : dcn_u16(0);
-    }
-    __syncthreads();
-    for (int e = tid; e < 32 * 64; e += kBlock) {   // write: channels fastest
-      const int pp = e >> 5, c = e & 31;
-      if (c0 + c < C && p0 + pp < HW) imT[(static_cast<size_t>(b) * HW + p0 + pp) * C + c0 + c] = tile[c][pp];
-    }
+    transpose_tile(tile, im, imT, C, HW, blockIdx.x);
     return;
   }
   const int64_t n = static_cast<int64_t>(Cout) * C * T;
@@ -1135,23 +1190,12 @@ dcn_fused_prep_kernel(const dcn_u16* __restrict__ im, const dcn_u16* __restrict_
   }
 }
 
-template <bool BF16> struct DcnConv;
-template <> struct DcnConv<false> {
-  static __device__ __forceinline__ float to_f(dcn_u16 v) { return __half2float(__ushort_as_half(v)); }
-  static __device__ __forceinline__ dcn_u16 from_f(float f) { return __half_as_ushort(__float2half(f)); }
-};
-template <> struct DcnConv<true> {
-  static __device__ __forceinline__ float to_f(dcn_u16 v) { return __uint_as_float(static_cast<unsigned>(v) << 16); }
-  static __device__ __forceinline__ dcn_u16 from_f(float f) {
-    const __hip_bfloat16 h = __float2bfloat16(f);
-    return *reinterpret_cast<const dcn_u16*>(&h);
-  }
-};
-
 // 8 channels of one tap (16 bytes) as a register vector (a struct of 16-bit fields is not promoted to registers:
 // the first version kept these staging arrays in scratch memory with a vmcnt(0) after every load)
 typedef unsigned int DcnRaw8 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dcn_u16 dcn_elem(const DcnRaw8& r, int e) { return static_cast<dcn_u16>((r[e >> 1] >> ((e & 1) * 16)) & 0xffffu); }
+template <typename T> __device__ __forceinline__ float dcn_elem(const DcnRaw8& r, int e) {
+  return Io<T>::ld(from_bits16<T>(static_cast<dcn_u16>((r[e >> 1] >> ((e & 1) * 16)) & 0xffffu)));
+}
 
 // BKC = channels of one tap per K-step (32 / 64 / 128).  Gather mapping: the BKC channels of a sampling
 // point are 2 * BKC CONTIGUOUS bytes of the NHWC copy, read by LPP = BKC / 8 adjacent lanes (16 bytes each) —
@@ -1162,7 +1206,6 @@ template <bool BF16, typename T, int BKC>
 __global__ void __launch_bounds__(kBlock)
 dcn_fused_fwd_kernel(const dcn_u16* __restrict__ imT, const dcn_u16* __restrict__ wt, const T* __restrict__ offset,
                      const T* __restrict__ mask, const T* __restrict__ bias, T* __restrict__ out, Geom g, int Cout) {
-  using CV = DcnConv<BF16>;
   constexpr int LPP = BKC / 8;                 // lanes per pixel
   constexpr int PPP = kBlock / LPP;            // pixels per pass
   constexpr int NP = kFN / PPP;                // passes per step (1, 2 or 4)
@@ -1253,9 +1296,9 @@ dcn_fused_fwd_kernel(const dcn_u16* __restrict__ imT, const dcn_u16* __restrict_
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         // same expression as the im2col kernel: w1*a1 + w2*a2 + w3*a3 + w4*a4 (taps outside contribute 0)
-        const float v = wq[ps][0] * CV::to_f(dcn_elem(raw[ps][0], e)) + wq[ps][1] * CV::to_f(dcn_elem(raw[ps][1], e)) +
-                        wq[ps][2] * CV::to_f(dcn_elem(raw[ps][2], e)) + wq[ps][3] * CV::to_f(dcn_elem(raw[ps][3], e));
-        o[e >> 1] |= static_cast<unsigned>(CV::from_f(mask ? v * mq[ps] : v)) << ((e & 1) * 16);
+        const float v = wq[ps][0] * dcn_elem<T>(raw[ps][0], e) + wq[ps][1] * dcn_elem<T>(raw[ps][1], e) +
+                        wq[ps][2] * dcn_elem<T>(raw[ps][2], e) + wq[ps][3] * dcn_elem<T>(raw[ps][3], e);
+        o[e >> 1] |= static_cast<unsigned>(bits16(Io<T>::st(mask ? v * mq[ps] : v))) << ((e & 1) * 16);
       }
       *reinterpret_cast<DcnRaw8*>(sB + (ps * PPP + pg) * LD + 8 * cq) = o;
     }
@@ -1343,7 +1386,7 @@ int dcn_fused_forward(const void* im, const void* weight, const void* offset, co
   dcn_u16* imT = reinterpret_cast<dcn_u16*>(base);
   dcn_u16* wt = reinterpret_cast<dcn_u16*>(base + im_bytes);
   const int HW = g.H * g.W, T_ = g.kh * g.kw;
-  const int nb_im = g.B * ((g.C + 31) / 32) * ((HW + 63) / 64);
+  const int nb_im = static_cast<int>(transpose_blocks(g.B, g.C, HW));
   const int nb_w = static_cast<int>(std::min<int64_t>(ceil_div64(static_cast<int64_t>(Cout) * g.C * T_, kBlock), 4 * kNumCU));
   hipLaunchKernelGGL(dcn_fused_prep_kernel, dim3(static_cast<unsigned>(nb_im + nb_w)), dim3(kBlock), 0, st_,
                      static_cast<const dcn_u16*>(im), static_cast<const dcn_u16*>(weight), imT, wt, g.B, g.C, HW, Cout, T_,
@@ -1386,78 +1429,27 @@ int dcn_fused_forward(const void* im, const void* weight, const void* offset, co
 // the gather moves contiguous Cout-vectors instead of single column elements.  Requires deformable_group == 1, conv
 // groups == 1 and C / V, Cout / V powers of two in [16, 256] (every model shape); anything else stays on the
 // reference-layout kernels above.
-template <typename T> struct VecT;
-template <> struct VecT<float> { static constexpr int N = 4; };
-template <> struct VecT<__half> { static constexpr int N = 8; };
-template <> struct VecT<__hip_bfloat16> { static constexpr int N = 8; };
-
-typedef unsigned int RawV4 __attribute__((ext_vector_type(4)));
-
-template <typename T> __device__ __forceinline__ void vec_load(const T* p, float* v);
-template <> __device__ __forceinline__ void vec_load<float>(const float* p, float* v) {
-  const float4 r = *reinterpret_cast<const float4*>(p);
-  v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-}
-template <> __device__ __forceinline__ void vec_load<__half>(const __half* p, float* v) {
-  const RawV4 r = *reinterpret_cast<const RawV4*>(p);
+// one 16-byte access of max_vec<T>() channels (4 fp32, 8 half) <-> fp32 registers
+template <typename T> __device__ __forceinline__ void vec_load(const T* p, float* v) {
+  constexpr int V = max_vec<T>();
+  const Vec<T, V> r = *reinterpret_cast<const Vec<T, V>*>(p);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __half2float(__ushort_as_half(static_cast<unsigned short>(r[i] & 0xffffu)));
-    v[2 * i + 1] = __half2float(__ushort_as_half(static_cast<unsigned short>(r[i] >> 16)));
-  }
+  for (int e = 0; e < V; ++e) v[e] = Io<T>::ld(r.v[e]);
 }
-template <> __device__ __forceinline__ void vec_load<__hip_bfloat16>(const __hip_bfloat16* p, float* v) {
-  const RawV4 r = *reinterpret_cast<const RawV4*>(p);
+template <typename T> __device__ __forceinline__ void vec_store(T* p, const float* v) {
+  constexpr int V = max_vec<T>();
+  Vec<T, V> r;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(r[i] << 16);
-    v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u);
-  }
-}
-template <typename T> __device__ __forceinline__ void vec_store(T* p, const float* v);
-template <> __device__ __forceinline__ void vec_store<float>(float* p, const float* v) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void vec_store<__half>(__half* p, const float* v) {
-  RawV4 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    r[i] = static_cast<unsigned>(__half_as_ushort(__float2half(v[2 * i]))) |
-           (static_cast<unsigned>(__half_as_ushort(__float2half(v[2 * i + 1]))) << 16);
-  *reinterpret_cast<RawV4*>(p) = r;
-}
-template <> __device__ __forceinline__ void vec_store<__hip_bfloat16>(__hip_bfloat16* p, const float* v) {
-  RawV4 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const __hip_bfloat16 a = __float2bfloat16(v[2 * i]), b = __float2bfloat16(v[2 * i + 1]);
-    r[i] = static_cast<unsigned>(*reinterpret_cast<const unsigned short*>(&a)) |
-           (static_cast<unsigned>(*reinterpret_cast<const unsigned short*>(&b)) << 16);
-  }
-  *reinterpret_cast<RawV4*>(p) = r;
+  for (int e = 0; e < V; ++e) r.v[e] = Io<T>::st(v[e]);
+  *reinterpret_cast<Vec<T, V>*>(p) = r;
 }
 
-// [B, C, HW] -> [B, HW, C] through a 32-channel x 64-pixel LDS tile (element size 2 or 4 bytes)
+// [B, C, HW] -> [B, HW, C]: transpose_tile, one workgroup a tile
 template <typename U>
 __global__ void __launch_bounds__(kBlock)
 nchw_to_nhwc_kernel(const U* __restrict__ in, U* __restrict__ out, int C, int HW) {
-  __shared__ U tile[32][64 + 4 / sizeof(U)];
-  const int tid = threadIdx.x;
-  const int pblocks = (HW + 63) / 64, cblocks = (C + 31) / 32;
-  int r = blockIdx.x;
-  const int pb = r % pblocks; r /= pblocks;
-  const int cb = r % cblocks;
-  const int b = r / cblocks;
-  const int p0 = pb * 64, c0 = cb * 32;
-  for (int e = tid; e < 32 * 64; e += kBlock) {   // read: pixels fastest
-    const int c = e >> 6, pp = e & 63;
-    tile[c][pp] = (c0 + c < C && p0 + pp < HW) ? in[(static_cast<size_t>(b) * C + c0 + c) * HW + p0 + pp] : U(0);
-  }
-  __syncthreads();
-  for (int e = tid; e < 32 * 64; e += kBlock) {   // write: channels fastest
-    const int pp = e >> 5, c = e & 31;
-    if (c0 + c < C && p0 + pp < HW) out[(static_cast<size_t>(b) * HW + p0 + pp) * C + c0 + c] = tile[c][pp];
-  }
+  __shared__ TransposeTile<U> tile;
+  transpose_tile(tile, in, out, C, HW, blockIdx.x);
 }
 
 // lanes per pixel / vectors per lane of a channel count (CV = channels / V, a power of two in [16, 256])
@@ -1472,26 +1464,12 @@ inline bool nhwc_map(int channels, int V, NhwcMap& m) {
   return true;
 }
 
-// the sampling point (b, tap, ho, wo) of deformable group 0
-template <typename T>
-__device__ __forceinline__ Sample tap_sample(const Geom& g, int b, int tap, int ho, int wo, int pix,
-                                             const T* __restrict__ offset, const T* __restrict__ mask, float& m) {
-  const int K = g.kh * g.kw;
-  const int i = tap / g.kw, j = tap - i * g.kw;
-  const size_t HWo = static_cast<size_t>(g.Ho) * g.Wo;
-  const T* op = offset + static_cast<size_t>(b) * 2 * K * HWo;
-  const float off_h = ld(op + (2 * tap) * HWo + pix), off_w = ld(op + (2 * tap + 1) * HWo + pix);
-  m = mask ? ld(mask + (static_cast<size_t>(b) * K + tap) * HWo + pix) : 1.f;
-  return make_sample(static_cast<float>(ho * g.stride_h - g.pad_h + i * g.dil_h) + off_h,
-                     static_cast<float>(wo * g.stride_w - g.pad_w + j * g.dil_w) + off_w, g.H, g.W);
-}
-
 // colT[q, tap, c] = mask * bilinear(xT[b, :, c]; sampling point (q, tap)), q = b * Ho * Wo + pix
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
 im2col_nhwc_kernel(const T* __restrict__ xT, const T* __restrict__ offset, const T* __restrict__ mask,
                    T* __restrict__ colT, Geom g, int sub, int nv, int64_t npix) {
-  constexpr int V = VecT<T>::N;
+  constexpr int V = max_vec<T>();
   const int ls = threadIdx.x % sub;
   const int64_t q = static_cast<int64_t>(blockIdx.x) * (kBlock / sub) + threadIdx.x / sub;
   if (q >= npix) return;
@@ -1500,10 +1478,10 @@ im2col_nhwc_kernel(const T* __restrict__ xT, const T* __restrict__ offset, const
   const int ho = pix / g.Wo, wo = pix - ho * g.Wo;
   const T* xb = xT + static_cast<size_t>(b) * g.H * g.W * g.C;
   for (int tap = 0; tap < K; ++tap) {
-    float m;
-    const Sample s = tap_sample(g, b, tap, ho, wo, pix, offset, mask, m);
-    const int idx[4] = {s.i1, s.i2, s.i3, s.i4};
-    const float wgt[4] = {s.w1 * m, s.w2 * m, s.w3 * m, s.w4 * m};
+    const Point pt{b, tap, ho, wo, pix};
+    const PointTaps taps = point_taps(pt, point_sample(pt, g, b, offset), point_mask(mask, g, b, tap, pix), g);
+    const auto& idx = taps.tgt;
+    const auto& wgt = taps.wgt;
     T* dst = colT + (static_cast<size_t>(q) * K + tap) * g.C;
     for (int k = 0; k < nv; ++k) {
       const int c = (k * sub + ls) * V;
@@ -1532,7 +1510,7 @@ __global__ void __launch_bounds__(kBlock)
 coord_nhwc_kernel(const T* __restrict__ colsG, const T* __restrict__ xT, const T* __restrict__ offset,
                   const T* __restrict__ mask, T* __restrict__ grad_offset, T* __restrict__ grad_mask, Geom g,
                   int sub, int nv, int64_t npix) {
-  constexpr int V = VecT<T>::N;
+  constexpr int V = max_vec<T>();
   const int ls = threadIdx.x % sub;
   const int64_t q0 = static_cast<int64_t>(blockIdx.x) * (kBlock / sub) + threadIdx.x / sub;
   const bool live = q0 < npix;                 // dead groups stay for the wave-wide shuffles
@@ -1543,8 +1521,8 @@ coord_nhwc_kernel(const T* __restrict__ colsG, const T* __restrict__ xT, const T
   const T* xb = xT + static_cast<size_t>(b) * g.H * g.W * g.C;
   const int lane = threadIdx.x & (kWave - 1);
   for (int tap = 0; tap < K; ++tap) {
-    float m;
-    const Sample s = tap_sample(g, b, tap, ho, wo, pix, offset, mask, m);
+    const Sample s = point_sample(Point{b, tap, ho, wo, pix}, g, b, offset);
+    const float m = point_mask(mask, g, b, tap, pix);
     const int idx[4] = {s.i1, s.i2, s.i3, s.i4};
     const float hw = 1.f - s.lw, hh = 1.f - s.lh;
     const float ch[4] = {-hw, -s.lw, hw, s.lw};          // d/dh weights of the four corners
@@ -1589,7 +1567,7 @@ template <typename T>
 __global__ void __launch_bounds__(kBlock)
 sampleT_gather_kernel(const T* __restrict__ gT, const int32_t* __restrict__ counter, const EllEntry* __restrict__ ent,
                       T* __restrict__ S_T, Geom g, int Cout, int sub, int nv, int64_t npix) {
-  constexpr int V = VecT<T>::N;
+  constexpr int V = max_vec<T>();
   const int ls = threadIdx.x % sub;
   const int64_t gp = static_cast<int64_t>(blockIdx.x) * (kBlock / sub) + threadIdx.x / sub;   // b * H * W + pixel
   if (gp >= npix) return;
@@ -1598,20 +1576,9 @@ sampleT_gather_kernel(const T* __restrict__ gT, const int32_t* __restrict__ coun
   for (int tap = 0; tap < K; ++tap) {
     const size_t col = (static_cast<size_t>(b) * K + tap) * HW + p;             // counter: [img][tap][pixel]
     const int n = min(counter[col], kEllCap);
-    const EllEntry* ee = ent + ((static_cast<size_t>(b) * K + tap) * HW + p) * kEllCap;
     int32_t qi[kEllCap];
     float wi[kEllCap];
-    // the pixel's whole 64-byte record in four 16-byte loads (same addresses across the pixel group); slots >= n may
-    // hold anything (the scatter build leaves them unwritten): they are replaced before use
-    const float4* rec = reinterpret_cast<const float4*>(ee);
-#pragma unroll
-    for (int j = 0; j < kEllCap; j += 2) {
-      const float4 r = rec[j / 2];
-      qi[j] = (j < n ? __float_as_int(r.x) : tap * (g.B * HWo)) - tap * (g.B * HWo);   // column index -> b * Ho * Wo + pix
-      wi[j] = j < n ? r.y : 0.f;
-      qi[j + 1] = (j + 1 < n ? __float_as_int(r.z) : tap * (g.B * HWo)) - tap * (g.B * HWo);
-      wi[j + 1] = j + 1 < n ? r.w : 0.f;
-    }
+    ell_record(ent + col * kEllCap, n, tap * (g.B * HWo), qi, wi);
     T* dst = S_T + (static_cast<size_t>(gp) * K + tap) * Cout;
     for (int k = 0; k < nv; ++k) {
       const int co = (k * sub + ls) * V;
@@ -1632,23 +1599,34 @@ sampleT_gather_kernel(const T* __restrict__ gT, const int32_t* __restrict__ coun
   }
 }
 
+// The overflow list of a deformable_group == 1 index added entry by entry, one packed atomic per channel pair (`channels` is
+// even in the plan): src(tap, q) is the row of `channels` values that entry (tap, sampling point q) reads, dst(li, tap) the
+// row it is added to (li = b * H * W + pixel).  A grid-stride loop: any grid, any lanes.
+template <typename T, typename Src, typename Dst>
+__device__ __forceinline__ void ell_overflow_add_pairs(const EllOverflow* __restrict__ ovf, int n, int channels, const Geom& g,
+                                                       Src src, Dst dst) {
+  const int half_c = channels / 2;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < static_cast<int64_t>(n) * half_c;
+       i += static_cast<int64_t>(gridDim.x) * kBlock) {
+    const int e = static_cast<int>(i / half_c);
+    const int c = 2 * static_cast<int>(i - static_cast<int64_t>(e) * half_c);
+    const EllOverflow o = ovf[e];
+    int tap, q;
+    ell_overflow_point(o, g, tap, q);
+    const T* s = src(tap, q) + c;
+    atomic_add2_t(dst(o.li, tap) + c, o.w * ld(s), o.w * ld(s + 1));
+  }
+}
+
 // contributions beyond kEllCap per (pixel, tap): added with atomics after the gather (rare)
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
 sampleT_overflow_kernel(const T* __restrict__ gT, const int32_t* __restrict__ ovf_count, const EllOverflow* __restrict__ ovf,
                         int ovf_cap, T* __restrict__ S_T, Geom g, int Cout) {
-  const int n = min(*ovf_count, ovf_cap);
-  const int HWo = g.Ho * g.Wo, K = g.kh * g.kw;
-  const int half_c = Cout / 2;                    // channel pairs: one packed atomic each (Cout is even in the plan)
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < static_cast<int64_t>(n) * half_c;
-       i += static_cast<int64_t>(gridDim.x) * kBlock) {
-    const int e = static_cast<int>(i / half_c);
-    const int co = 2 * static_cast<int>(i - static_cast<int64_t>(e) * half_c);
-    const EllOverflow o = ovf[e];                 // li = b * H * W + pixel (dg == 1), colidx = tap * B * HWo + q
-    const int tap = o.colidx / (g.B * HWo), q = o.colidx - tap * (g.B * HWo);
-    const T* src = gT + static_cast<size_t>(q) * Cout + co;
-    atomic_add2_t(S_T + (static_cast<size_t>(o.li) * K + tap) * Cout + co, o.w * ld(src), o.w * ld(src + 1));
-  }
+  const int K = g.kh * g.kw;
+  ell_overflow_add_pairs<T>(ovf, min(*ovf_count, ovf_cap), Cout, g,
+                            [&](int, int q) { return gT + static_cast<size_t>(q) * Cout; },
+                            [&](int32_t li, int tap) { return S_T + (static_cast<size_t>(li) * K + tap) * Cout; });
 }
 
 // grad_in_T[p, c] = sum over taps and over the sampling points (q, tap) whose bilinear footprint contains pixel p of
@@ -1660,7 +1638,7 @@ template <typename T>
 __global__ void __launch_bounds__(kBlock)
 col2im_nhwc_gather_kernel(const T* __restrict__ colsG, const int32_t* __restrict__ counter, const EllEntry* __restrict__ ent,
                           T* __restrict__ ginT, Geom g, int sub, int nv, int64_t npix) {
-  constexpr int V = VecT<T>::N;
+  constexpr int V = max_vec<T>();
   constexpr int kMaxNv = 4;                       // C / V <= 256 lanes-vectors, sub = min(C / V, 64)
   const int ls = threadIdx.x % sub;
   const int64_t gp = static_cast<int64_t>(blockIdx.x) * (kBlock / sub) + threadIdx.x / sub;   // b * H * W + pixel
@@ -1675,17 +1653,9 @@ col2im_nhwc_gather_kernel(const T* __restrict__ colsG, const int32_t* __restrict
   for (int tap = 0; tap < K; ++tap) {
     const size_t col = (static_cast<size_t>(b) * K + tap) * HW + p;             // counter: [img][tap][pixel]
     const int n = min(counter[col], kEllCap);
-    const float4* rec = reinterpret_cast<const float4*>(ent + col * kEllCap);
     int32_t qi[kEllCap];
     float wi[kEllCap];
-#pragma unroll
-    for (int j = 0; j < kEllCap; j += 2) {
-      const float4 r = rec[j / 2];
-      qi[j] = (j < n ? __float_as_int(r.x) : tap * (g.B * HWo)) - tap * (g.B * HWo);   // column index -> b * Ho * Wo + pix
-      wi[j] = j < n ? r.y : 0.f;
-      qi[j + 1] = (j + 1 < n ? __float_as_int(r.z) : tap * (g.B * HWo)) - tap * (g.B * HWo);
-      wi[j + 1] = j + 1 < n ? r.w : 0.f;
-    }
+    ell_record(ent + col * kEllCap, n, tap * (g.B * HWo), qi, wi);
 #pragma unroll
     for (int j = 0; j < kEllCap; ++j) {
       if (j < n) {                                 // uniform over the pixel's lane group
@@ -1725,7 +1695,7 @@ col2im_nhwc_overflow_kernel(const T* __restrict__ colsG, const int32_t* __restri
   __shared__ int s_dup, s_nm;
   __shared__ int s_match[kOvfReduceMax];
   const int n = min(*ovf_count, ovf_cap);
-  const int HWo = g.Ho * g.Wo, K = g.kh * g.kw, C = g.C;
+  const int K = g.kh * g.kw, C = g.C;
   if (n <= kOvfReduceMax) {
     for (int e = blockIdx.x; e < n; e += gridDim.x) {   // block-uniform control flow throughout
       const int32_t li = ovf[e].li;                     // li = b * H * W + pixel (dg == 1)
@@ -1744,8 +1714,9 @@ col2im_nhwc_overflow_kernel(const T* __restrict__ colsG, const int32_t* __restri
         for (int c = 2 * threadIdx.x; c < C; c += 2 * kBlock) {
           float a0 = 0.f, a1 = 0.f;
           for (int k = 0; k < m; ++k) {
-            const EllOverflow o = ovf[s_match[k]];      // colidx = tap * B * HWo + q
-            const int tap = o.colidx / (g.B * HWo), q = o.colidx - tap * (g.B * HWo);
+            const EllOverflow o = ovf[s_match[k]];
+            int tap, q;
+            ell_overflow_point(o, g, tap, q);
             const T* src = colsG + (static_cast<size_t>(q) * K + tap) * C + c;
             a0 = fmaf(o.w, ld(src), a0);
             a1 = fmaf(o.w, ld(src + 1), a1);
@@ -1759,22 +1730,14 @@ col2im_nhwc_overflow_kernel(const T* __restrict__ colsG, const int32_t* __restri
     }
     return;
   }
-  const int half_c = C / 2;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < static_cast<int64_t>(n) * half_c;
-       i += static_cast<int64_t>(gridDim.x) * kBlock) {
-    const int e = static_cast<int>(i / half_c);
-    const int c = 2 * static_cast<int>(i - static_cast<int64_t>(e) * half_c);
-    const EllOverflow o = ovf[e];                 // li = b * H * W + pixel (dg == 1), colidx = tap * B * HWo + q
-    const int tap = o.colidx / (g.B * HWo), q = o.colidx - tap * (g.B * HWo);
-    const T* src = colsG + (static_cast<size_t>(q) * K + tap) * C + c;
-    atomic_add2_t(ginT + static_cast<size_t>(o.li) * C + c, o.w * ld(src), o.w * ld(src + 1));
-  }
+  ell_overflow_add_pairs<T>(ovf, n, C, g, [&](int tap, int q) { return colsG + (static_cast<size_t>(q) * K + tap) * C; },
+                            [&](int32_t li, int) { return ginT + static_cast<size_t>(li) * C; });
 }
 
 template <typename T>
 int nchw_to_nhwc_t(const void* in, void* out, int B, int C, int HW, hipStream_t st_) {
-  if (static_cast<int64_t>(B) * ((HW + 63) / 64) * ((C + 31) / 32) > 0x7fffffff) return DETOPS_EUNSUPPORTED;
-  const dim3 grid(static_cast<unsigned>(B * ((HW + 63) / 64) * ((C + 31) / 32)));
+  if (transpose_blocks(B, C, HW) > 0x7fffffff) return DETOPS_EUNSUPPORTED;
+  const dim3 grid(static_cast<unsigned>(transpose_blocks(B, C, HW)));
   if (sizeof(T) == 4)
     hipLaunchKernelGGL(nchw_to_nhwc_kernel<unsigned int>, grid, dim3(kBlock), 0, st_, static_cast<const unsigned int*>(in),
                        static_cast<unsigned int*>(out), C, HW);
@@ -1784,13 +1747,20 @@ int nchw_to_nhwc_t(const void* in, void* out, int B, int C, int HW, hipStream_t 
   return launch_status();
 }
 
+// the gate of every channels-last launcher: deformable_group == 1 and `channels` inside the lane plan (else the caller
+// stays on the reference-layout entry points); the grid is one lane group a pixel
+template <typename T> inline bool nhwc_launch_map(const Geom& g, int channels, NhwcMap& m) {
+  return g.dg == 1 && nhwc_map(channels, max_vec<T>(), m);
+}
+inline dim3 nhwc_grid(int64_t npix, const NhwcMap& m) { return dim3(static_cast<unsigned>(ceil_div64(npix, m.ppb))); }
+
 template <typename T>
 int im2col_nhwc_t(const void* xT, const void* offset, const void* mask, void* colT, const Geom& g, hipStream_t st_) {
   NhwcMap m;
-  if (g.dg != 1 || !nhwc_map(g.C, VecT<T>::N, m)) return DETOPS_EUNSUPPORTED;
+  if (!nhwc_launch_map<T>(g, g.C, m)) return DETOPS_EUNSUPPORTED;
   const int64_t npix = static_cast<int64_t>(g.B) * g.Ho * g.Wo;
   if (npix == 0) return 0;
-  hipLaunchKernelGGL(im2col_nhwc_kernel<T>, dim3(static_cast<unsigned>(ceil_div64(npix, m.ppb))), dim3(kBlock), 0, st_,
+  hipLaunchKernelGGL(im2col_nhwc_kernel<T>, nhwc_grid(npix, m), dim3(kBlock), 0, st_,
                      static_cast<const T*>(xT), static_cast<const T*>(offset), static_cast<const T*>(mask),
                      static_cast<T*>(colT), g, m.sub, m.nv, npix);
   return launch_status();
@@ -1800,10 +1770,10 @@ template <typename T>
 int coord_nhwc_t(const void* colsG, const void* xT, const void* offset, const void* mask, void* goff, void* gmask,
                  const Geom& g, hipStream_t st_) {
   NhwcMap m;
-  if (g.dg != 1 || !nhwc_map(g.C, VecT<T>::N, m)) return DETOPS_EUNSUPPORTED;
+  if (!nhwc_launch_map<T>(g, g.C, m)) return DETOPS_EUNSUPPORTED;
   const int64_t npix = static_cast<int64_t>(g.B) * g.Ho * g.Wo;
   if (npix == 0) return 0;
-  hipLaunchKernelGGL(coord_nhwc_kernel<T>, dim3(static_cast<unsigned>(ceil_div64(npix, m.ppb))), dim3(kBlock), 0, st_,
+  hipLaunchKernelGGL(coord_nhwc_kernel<T>, nhwc_grid(npix, m), dim3(kBlock), 0, st_,
                      static_cast<const T*>(colsG), static_cast<const T*>(xT), static_cast<const T*>(offset),
                      static_cast<const T*>(mask), static_cast<T*>(goff), static_cast<T*>(gmask), g, m.sub, m.nv, npix);
   return launch_status();
@@ -1813,20 +1783,16 @@ template <typename T>
 int sampleT_t(const void* gT, const void* offset, const void* mask, void* S_T, const Geom& g, int Cout, const EllPlan& P,
               void* ws, hipStream_t st_) {
   NhwcMap m;
-  if (g.dg != 1 || !nhwc_map(Cout, VecT<T>::N, m)) return DETOPS_EUNSUPPORTED;
+  if (!nhwc_launch_map<T>(g, Cout, m)) return DETOPS_EUNSUPPORTED;
   const int64_t npix = static_cast<int64_t>(g.B) * g.H * g.W;
   if (npix == 0 || P.npoints_per_dg == 0) return 0;
-  char* w = static_cast<char*>(ws);
-  int32_t* count = reinterpret_cast<int32_t*>(w + P.off_count);
-  int32_t* ovf_count = reinterpret_cast<int32_t*>(w + P.off_ovf_count);
-  EllEntry* ent = reinterpret_cast<EllEntry*>(w + P.off_ent);
-  EllOverflow* ovf = reinterpret_cast<EllOverflow*>(w + P.off_ovf);
-  { const int rc = ell_build<T>(offset, mask, g, P, count, ovf_count, ent, ovf, P.off_ent - P.off_count, st_); if (rc) return rc; }
-  hipLaunchKernelGGL(sampleT_gather_kernel<T>, dim3(static_cast<unsigned>(ceil_div64(npix, m.ppb))), dim3(kBlock), 0, st_,
-                     static_cast<const T*>(gT), static_cast<const int32_t*>(count), static_cast<const EllEntry*>(ent),
+  const EllIndex ix = ell_index(ws, P);
+  if (const int rc = ell_build<T>(offset, mask, g, P, ix, st_)) return rc;
+  hipLaunchKernelGGL(sampleT_gather_kernel<T>, nhwc_grid(npix, m), dim3(kBlock), 0, st_,
+                     static_cast<const T*>(gT), static_cast<const int32_t*>(ix.count), static_cast<const EllEntry*>(ix.ent),
                      static_cast<T*>(S_T), g, Cout, m.sub, m.nv, npix);
   hipLaunchKernelGGL(sampleT_overflow_kernel<T>, dim3(kNumCU), dim3(kBlock), 0, st_, static_cast<const T*>(gT),
-                     static_cast<const int32_t*>(ovf_count), static_cast<const EllOverflow*>(ovf), P.ovf_cap,
+                     static_cast<const int32_t*>(ix.ovf_count), static_cast<const EllOverflow*>(ix.ovf), P.ovf_cap,
                      static_cast<T*>(S_T), g, Cout);
   return launch_status();
 }
@@ -1835,24 +1801,20 @@ template <typename T>
 int col2im_nhwc_t(const void* colsG, const void* offset, const void* mask, void* ginT, const Geom& g, const EllPlan& P, void* ws,
                   hipStream_t st_) {
   NhwcMap m;
-  if (g.dg != 1 || !nhwc_map(g.C, VecT<T>::N, m) || m.nv > 4) return DETOPS_EUNSUPPORTED;
+  if (!nhwc_launch_map<T>(g, g.C, m) || m.nv > 4) return DETOPS_EUNSUPPORTED;
   const int64_t npix = static_cast<int64_t>(g.B) * g.H * g.W;
   if (npix == 0) return 0;
   if (P.npoints_per_dg == 0) {
     DETOPS_HIP_TRY(hipMemsetAsync(ginT, 0, sizeof(T) * static_cast<size_t>(npix) * g.C, st_));
     return 0;
   }
-  char* w = static_cast<char*>(ws);
-  int32_t* count = reinterpret_cast<int32_t*>(w + P.off_count);
-  int32_t* ovf_count = reinterpret_cast<int32_t*>(w + P.off_ovf_count);
-  EllEntry* ent = reinterpret_cast<EllEntry*>(w + P.off_ent);
-  EllOverflow* ovf = reinterpret_cast<EllOverflow*>(w + P.off_ovf);
-  { const int rc = ell_build<T>(offset, mask, g, P, count, ovf_count, ent, ovf, P.off_ent - P.off_count, st_); if (rc) return rc; }
-  hipLaunchKernelGGL(col2im_nhwc_gather_kernel<T>, dim3(static_cast<unsigned>(ceil_div64(npix, m.ppb))), dim3(kBlock), 0, st_,
-                     static_cast<const T*>(colsG), static_cast<const int32_t*>(count), static_cast<const EllEntry*>(ent),
+  const EllIndex ix = ell_index(ws, P);
+  if (const int rc = ell_build<T>(offset, mask, g, P, ix, st_)) return rc;
+  hipLaunchKernelGGL(col2im_nhwc_gather_kernel<T>, nhwc_grid(npix, m), dim3(kBlock), 0, st_,
+                     static_cast<const T*>(colsG), static_cast<const int32_t*>(ix.count), static_cast<const EllEntry*>(ix.ent),
                      static_cast<T*>(ginT), g, m.sub, m.nv, npix);
   hipLaunchKernelGGL(col2im_nhwc_overflow_kernel<T>, dim3(kNumCU), dim3(kBlock), 0, st_, static_cast<const T*>(colsG),
-                     static_cast<const int32_t*>(ovf_count), static_cast<const EllOverflow*>(ovf), P.ovf_cap,
+                     static_cast<const int32_t*>(ix.ovf_count), static_cast<const EllOverflow*>(ix.ovf), P.ovf_cap,
                      static_cast<T*>(ginT), g);
   return launch_status();
 }

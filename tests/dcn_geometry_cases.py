@@ -459,3 +459,104 @@ def check_ref_layout_rect(device, c, col2im, ell_build):
     rgoff, rgm = oracle.deformable_col2im_coord(gcol, i["x"], i["off"], i["mask"], **ogeo)
     _bit_equal(goff, rgoff, f32, c.name + " col2im_coord offset")
     _bit_equal(gm, rgm, f32, c.name + " col2im_coord mask")
+
+
+# ---------------------------------------------------------------------------------------------- 16-bit atomics (scatter, overflow list)
+# An odd plane (35 elements: channel planes start on both halves of a dword), two deformable groups.  HALF_ATOMIC_TALL is the
+# same map three tiles high (plane of 147): col2im_tile_kernel's LDS window of the first 8-row tile ends at input row 13, so
+# taps of output row 7 displaced by 6 rows land in the map but outside the window and take that kernel's DIRECT global
+# atomics; at 5 x 7 the window covers the whole map and every add reaches the 16-bit atomic through the window's flush.
+HALF_ATOMIC = _c("half-atomic-5x7", 1, 4, 5, 7, 4, 3, 1, 1, 1, 2)
+HALF_ATOMIC_TALL = _c("half-atomic-21x7", 1, 4, 21, 7, 4, 3, 1, 1, 1, 2)
+HALF_ATOMIC_PILE = 10                 # sampling points of one tap steered onto one pixel (against the index's 8 slots)
+HALF_ATOMIC_BOUND = 32.0              # 256 quanta of 1/8: every partial sum below it is a bf16 (and fp16) number
+
+
+def _half_atomic_draw(c, seed):
+    """offsets in multiples of 1/2 (bilinear weights in multiples of 1/4), mask in {0.5, 1}, integer column gradient in
+    [-2, 2]: every product is a multiple of 1/8.  Most offsets stay within the scatter's 4-pixel halo; one output row of
+    group 1 is displaced by 6 (along the axis on which part of it stays inside the map); about 4 % of the pairs point
+    outside the map; HALF_ATOMIC_PILE points of the centre tap of group 0 are steered exactly onto pixel (2, 3), where
+    each has weight 1."""
+    rng = np.random.RandomState(seed)
+    Ho, Wo = out_hw(c)
+    K = c.kh * c.kw
+    off = rng.randint(-8, 9, (c.B, c.dg, K, 2, Ho, Wo)) / 2.0
+    far = rng.rand(c.B, c.dg, K, 1, Ho, Wo) < 0.04
+    off = np.where(far, off + 12.0, off)
+    if c.H > 8:
+        off[:, 1, :, 0, 7, :] = 6.0                              # output row 7, 6 rows down: input rows 12 .. 14 of the tall map
+    else:
+        off[:, 1, :, 1, 2, :] = 6.0                              # output row 2, 6 columns right: columns 5 and 6, the rest outside
+    tap = (c.kh // 2) * c.kw + c.kw // 2
+    for n in range(HALF_ATOMIC_PILE):
+        ho, wo = divmod(n * 3 % (Ho * Wo), Wo)
+        off[0, 0, tap, 0, ho, wo] = 2 - ho                       # centre tap, pad 1, stride 1: samples (ho + off_h, wo + off_w)
+        off[0, 0, tap, 1, ho, wo] = 3 - wo
+    f = np.float32
+    return dict(off=off.reshape(c.B, c.dg * 2 * K, Ho, Wo).astype(f),
+                mask=rng.choice([0.5, 1.0], (c.B, c.dg * K, Ho, Wo)).astype(f),
+                gcol=rng.randint(-2, 3, (c.C * K, c.B * Ho * Wo)).astype(f))
+
+
+def half_atomic_problem(c):
+    """-> (inputs, oracle's fp32 result of 1 + col2im).  The result is bit-equal in any summation order and with every add
+    rounded to fp16 / bf16 only if every partial sum is exactly representable, so the seed is chosen HERE, on the oracle alone,
+    such that 1 + col2im(|gcol|) stays below HALF_ATOMIC_BOUND for every element — a condition on the inputs, not a
+    tolerance — and (5 x 7) such that the pile-up is there: the centre tap's weights on pixel (2, 3) of group 0 sum to more
+    than 8 and no weight exceeds 1, so more than 8 sampling points of that (pixel, tap) contribute."""
+    key = (c, "half-atomic")
+    if key in _PROBLEMS:
+        return _PROBLEMS[key]
+    ogeo = dict(kh=c.kh, kw=c.kw, pad=c.pad, stride=c.stride, dil=c.dil, dg=c.dg)
+    shape = (c.B, c.C, c.H, c.W)
+    K = c.kh * c.kw
+    for seed in range(200):
+        d = _half_atomic_draw(c, 4000 + seed)
+        worst = 1.0 + oracle.deformable_col2im(np.abs(d["gcol"]), d["off"], d["mask"], *shape, **ogeo)
+        if float(worst.max()) < HALF_ATOMIC_BOUND:
+            break
+    assert float(worst.max()) < HALF_ATOMIC_BOUND and float(worst.min()) >= 1.0, (c.name, float(worst.max()))
+    onehot = np.zeros_like(d["gcol"])
+    onehot[(c.kh // 2) * c.kw + c.kw // 2] = 1.0                   # channel 0 (group 0), centre tap
+    hits = oracle.deformable_col2im(onehot, d["off"], None, *shape, **ogeo)
+    assert float(hits[0, 0, 2, 3]) > 8.0, (c.name, float(hits[0, 0, 2, 3]))
+    want = np.float32(1.0) + oracle.deformable_col2im(d["gcol"], d["off"], d["mask"], *shape, **ogeo)
+    for a in list(d.values()) + [want]:
+        a.setflags(write=False)
+    _PROBLEMS[key] = (d, want)
+    return _PROBLEMS[key]
+
+
+def check_half_atomic_col2im(device, c, dtype, col2im, ell_build=0):
+    """`_C.deformable_col2im` (v2) in fp16 / bf16 on `half_atomic_problem`, accumulated into a map pre-filled with 1, with the
+    kernel forced: dcn_col2im = 2, the scatter (col2im_tile_kernel: 16-bit compare-and-swap adds from the window's flush and,
+    on the tall map, from the direct branch); dcn_col2im = 3, the fixed-width index, whose (pixel, tap) with more than 8
+    contributions goes through col2im_ell_overflow_kernel's 16-bit adds, under both index builds.  Bit-equal to the oracle's
+    fp32 result cast to the storage type."""
+    from maskrcnn_benchmark import _C
+    d, want = half_atomic_problem(c)
+    set_tuning(device, "dcn_col2im", col2im)
+    set_tuning(device, "dcn_ell_build", ell_build)
+    t = {k: torch.from_numpy(np.array(a)).to(device=device, dtype=dtype) for k, a in d.items()}
+    gim = torch.ones((c.B, c.C, c.H, c.W), device=device, dtype=dtype)
+    with launches() as calls:
+        _C.deformable_col2im(t["gcol"], t["off"], t["mask"], gim, c.kh, c.kw, c.pad[0], c.pad[1], c.stride[0], c.stride[1],
+                             c.dil[0], c.dil[1], c.dg)
+    assert _dcn(calls) == {"dcn_col2im": 1}, calls
+    _bit_equal(gim, want, dtype, "%s col2im (dcn_col2im = %d, dcn_ell_build = %d)" % (c.name, col2im, ell_build))
+
+
+# ---------------------------------------------------------------------------------------------- layout transposition, ragged tiles
+def check_to_nhwc_tails(device, dtype):
+    """`_C._to_nhwc` (nchw_to_nhwc_kernel) on [2, 33, 5, 13]: one channel past a 32-channel block, one pixel past a 64-pixel
+    block (H * W = 65) — a copy: equal to the permuted input exactly.  (The same tile copy inside dcn_fused_prep_kernel is
+    held bit-equal at ragged pixel tiles by FUSED_CASES: 9 x 11 = 99 pixels and 7 x 9 = 63; its channel count is always a
+    multiple of 32.)"""
+    from maskrcnn_benchmark import _C
+    x = torch.from_numpy(np.random.RandomState(11).randint(-1000, 1000, (2, 33, 5, 13)).astype(np.float32)).to(device=device, dtype=dtype)
+    with launches() as calls:
+        y = _C._to_nhwc(x)
+    assert _dcn(calls) == {"dcn_to_nhwc": 1}, calls
+    assert y.shape == (2, 65, 33) and y.dtype == dtype
+    assert torch.equal(y.cpu(), x.permute(0, 2, 3, 1).reshape(2, 65, 33).cpu())

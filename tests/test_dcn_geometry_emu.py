@@ -133,3 +133,21 @@ def test_overflow_list_half_input_gradient(monkeypatch, dtype, case, landing, in
 @pytest.mark.parametrize("case", G.REF_RECT_CASES, ids=_id)
 def test_reference_layout_kernels_rectangular_are_bit_equal_to_the_oracle(case, col2im, ell_build):
     G.check_ref_layout_rect(DEV, case, col2im, ell_build)
+
+
+# ---------------------------------------------------------------------------------------------- 16-bit atomics, ragged transposes
+@pytest.mark.parametrize("dtype", HALF, ids=_id)
+@pytest.mark.parametrize("case", [G.HALF_ATOMIC, G.HALF_ATOMIC_TALL], ids=_id)
+def test_scatter_col2im_half_is_bit_equal_to_the_rounded_oracle(case, dtype):
+    G.check_half_atomic_col2im(DEV, case, dtype, 2)
+
+
+@pytest.mark.parametrize("ell_build", [0, 1])
+@pytest.mark.parametrize("dtype", HALF, ids=_id)
+def test_ell_overflow_col2im_half_is_bit_equal_to_the_rounded_oracle(dtype, ell_build):
+    G.check_half_atomic_col2im(DEV, G.HALF_ATOMIC, dtype, 3, ell_build)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=_id)
+def test_to_nhwc_ragged_channel_and_pixel_tiles(dtype):
+    G.check_to_nhwc_tails(DEV, dtype)
