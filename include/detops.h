@@ -642,6 +642,48 @@ int detops_rle_string_write(const int32_t* counts, const int64_t* run_offset, in
                             const int64_t* byte_offset, uint8_t* out, const void* workspace, size_t workspace_bytes,
                             detops_stream_t stream);
 
+/* ---- Reading compressed RLE strings (csrc/rle_decode.hip) -----------------------------------------------------------------
+ * The inverse of the coding above: a restatement of pycocotools' rleFrString, written from knowledge of that code and,
+ * like the coder, never run against it.  For the bytes of one mask's string:
+ *   - a value is a maximal group of bytes that ends at the first byte b with ((b - 48) & 0x20) == 0;
+ *   - its 5-bit groups are assembled from the low end: x |= ((b - 48) & 0x1f) << 5k for the group's k-th byte;
+ *   - if the last group has bit 0x10 set, the value is sign-extended: x |= -1 << 5k (k = the number of bytes); x is a
+ *     signed 64-bit value;
+ *   - c[i] = x[i] for i <= 2, c[i] = x[i] + c[i - 2] for i > 2: two interleaved running sums that start at runs 1 and 2;
+ *     c[0] stands alone.  The runs are stored as int32.
+ * Malformed input is data.  A string's last byte ends a value whatever its continuation bit says; a value of more than
+ * 7 bytes is read from its last 7; (b - 48) is taken modulo 256; sums wrap in 64 bits.  status [N] int32 reports per mask:
+ *   DETOPS_RLE_BAD_BYTE    a byte outside 48..111
+ *   DETOPS_RLE_TRUNCATED   the last byte has the continuation bit set
+ *   DETOPS_RLE_LONG_VALUE  a value of more than 7 bytes
+ *   DETOPS_RLE_BAD_RUN     a run below 0 or at or above 2^31 after the sums
+ *   DETOPS_RLE_BAD_SUM     the runs do not sum to h * w (only when hw [N, 2] int32 is passed)
+ * The runs of a flagged mask are unspecified (here: what the rules above give, truncated to int32) but in bounds.
+ *
+ * detops_rle_decode_count / _write — bytes [B] uint8 and byte_offset [N + 1] int64 (byte_offset[0] = 0, non-decreasing,
+ *   byte_offset[N] = B) as detops_rle_string_write leaves them, or as the strings of a result file concatenated.
+ *     _count: run_offset [N + 1] int64 (device) = exclusive sum of the masks' numbers of values;
+ *     the caller reads run_offset[N] = total (the one host read of the path) and allocates counts [total] int32;
+ *     _write: fills counts and status (hw may be null).
+ *   Both calls take the same workspace of detops_rle_decode_workspace_bytes(B, N) bytes, untouched in between.  The work
+ *   is cut by chunks of the flat byte array, not by mask; a value is decoded by the thread that holds its last byte,
+ *   which walks back over at most 6 bytes; the running sums and the status bits are differences of plain prefix sums
+ *   taken in a fixed order (no atomics): every element of counts, run_offset and status is written exactly once, nothing
+ *   outside them, nothing is read outside bytes [0, B) whatever the bytes hold, and two runs give identical output.
+ *   Returns: DETOPS_EINVAL for N < 0, B < 0, total < 0 or a null pointer; DETOPS_EWORKSPACE for a workspace smaller than
+ *   the query's answer.  N == 0 or B == 0 (only empty strings) returns 0 with nothing launched and nothing written. */
+#define DETOPS_RLE_BAD_BYTE 1
+#define DETOPS_RLE_TRUNCATED 2
+#define DETOPS_RLE_LONG_VALUE 4
+#define DETOPS_RLE_BAD_RUN 8
+#define DETOPS_RLE_BAD_SUM 16
+size_t detops_rle_decode_workspace_bytes(int64_t B, int N);
+int detops_rle_decode_count(const uint8_t* bytes, const int64_t* byte_offset, int64_t B, int N, int64_t* run_offset,
+                            void* workspace, size_t workspace_bytes, detops_stream_t stream);
+int detops_rle_decode_write(const uint8_t* bytes, const int64_t* byte_offset, int64_t B, int N, const int64_t* run_offset,
+                            int64_t total, const int32_t* hw, int32_t* counts, int32_t* status, void* workspace,
+                            size_t workspace_bytes, detops_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Polygon instance masks (extensions; the reference rasterises polygons one ROI at a time on the CPU through pycocotools:
  * structures/segmentation_mask.py:273-335, roi_heads/mask_head/loss.py:11-42, "FIXME: CPU computation bottleneck").
@@ -704,6 +746,16 @@ int detops_polygons_to_masks(const float* verts, const int32_t* poly_offset, con
  *   extents (first row, last row, first word column, last word column), (H, -1, ceil(W / 64), -1) for an empty plane.
  *   Counts and extents are combined with integer atomics: deterministic.  max_words: the largest H * ceil(W / 64) of
  *   the call (sizes the grid; speed only).  Every word is written exactly once.
+ * detops_mask_pack_rle — the same five results from uncompressed RLE, no plane stored: counts
+ *   [total] int32 and run_offset [N + 1] int64 as detops_paste_masks_rle_write or detops_rle_decode_write make them,
+ *   plane_hw [N, 2].  Runs are column-major and start with a 0-run: pixel (y, x) is set iff position x * H + y lies in an
+ *   odd-indexed run; zero-length runs are legal and only toggle; area is the sum of the odd runs.  Runs that do not sum to
+ *   H * W are malformed: positions beyond the runs are 0, runs beyond H * W and negative runs are ignored.  words,
+ *   word_offset, area and extent as detops_mask_pack (layout, zero bits at and beyond W, empty-plane extents), every word
+ *   written exactly once, atomics for areas and extents only.  max_h / max_w: the largest H and W of the call.  THE
+ *   LARGEST H SERVED IS DETOPS_MASK_PACK_RLE_MAX_H (a strip of 64 columns lives in LDS as bits): with max_h above it the
+ *   entry point returns DETOPS_EUNSUPPORTED with nothing launched, and the caller packs that call on the host.
+ *   workspace: >= detops_mask_pack_rle_workspace_bytes(total) bytes, else DETOPS_EWORKSPACE.
  * detops_mask_pair_counts — counts [total_pairs] int32: for every (detection, ground truth) pair of every problem, the
  *   pixels set in both planes: popcount of the AND over the words inside the intersection of the two extents.  Pairs
  *   with disjoint extents read no plane; a pair whose planes differ in (H, W) gets -1 and reads none.  Every element
@@ -754,6 +806,11 @@ int detops_polygons_to_masks(const float* verts, const int32_t* poly_offset, con
 int detops_mask_pack(const unsigned char* planes, const int64_t* plane_offset, const int32_t* plane_hw, int N,
                      int64_t max_words, const int64_t* word_offset, uint64_t* words, int32_t* area, int32_t* extent,
                      detops_stream_t stream);
+#define DETOPS_MASK_PACK_RLE_MAX_H 4096
+size_t detops_mask_pack_rle_workspace_bytes(int64_t total);
+int detops_mask_pack_rle(const int32_t* counts, const int64_t* run_offset, int64_t total, const int32_t* plane_hw, int N,
+                         int max_h, int max_w, const int64_t* word_offset, uint64_t* words, int32_t* area, int32_t* extent,
+                         void* workspace, size_t workspace_bytes, detops_stream_t stream);
 int detops_mask_pair_counts(const uint64_t* dt_words, const int64_t* dt_word_offset, const int32_t* dt_hw,
                             const int32_t* dt_extent, const uint64_t* gt_words, const int64_t* gt_word_offset,
                             const int32_t* gt_hw, const int32_t* gt_extent, const int32_t* dt_offset, const int32_t* gt_offset,

@@ -3,6 +3,7 @@
 //
 //   detops_mask_pack          uint8 planes -> bit rows (a wave's __ballot over 64 consecutive pixels of a row is one word),
 //                             the planes' set-pixel counts and tight extents
+//   detops_mask_pack_rle      the same results straight from uncompressed RLE runs, no plane stored
 //   detops_mask_pair_counts   popcount(AND) over the intersection of two planes' extents, one wave per pair
 //   detops_eval_iou           counts or boxes -> the fp64 IoU matrix of every problem (COCO segm / COCO bbox / VOC)
 //   detops_eval_match         greedy matching, one wave per problem (COCO: a lane per (area range, threshold); VOC)
@@ -101,6 +102,139 @@ mask_pack_kernel(const unsigned char* __restrict__ planes, const int64_t* __rest
     atomicMax(&extent[4 * n + 3], cmax);
   }
 }
+
+// ---------------------------------------------------------------------------------------------------- pack from runs
+// detops_mask_pack_rle: uncompressed RLE (column-major runs starting with a 0-run) straight to the results of the pack
+// above; no plane is ever stored.
+//   1. start[i] = sum of the runs in front of run i of the FLAT run array (block_scan inside a chunk, scan_tiles over the
+//      chunks); a run's first position inside its mask is start[i] - start[run_offset[n]].
+//   2. A workgroup owns one mask and one strip of 64 columns at a time.  The strip lives in LDS as a COLUMN-major bit
+//      array, ceil(H / 64) words per column (padded to an odd number of words: the 32 lanes of a half wave then read 32
+//      different bank pairs).  A thread owns whole words of it: it finds the run that holds its word's first position by
+//      bisection of `start` and walks the runs that overlap the word — every LDS word is written once, by one thread.
+//   3. A wave turns 64 rows x 64 columns around with 64 ballots (lane = column, the trick of mask_pack_kernel), counts
+//      the pixels and narrows the extents on the way; lane b stores row 64 r + b's word.
+// Integer atomics only where mask_pack_kernel has them: one add and four min / max per wave that saw a pixel.
+constexpr int kRunPer = 8;                                    // consecutive runs of a thread of the scan
+constexpr int kRunChunk = kBlock * kRunPer;
+constexpr int kPackRleMaxH = DETOPS_MASK_PACK_RLE_MAX_H;
+constexpr int kColWords = (kPackRleMaxH / 64) | 1;                // words of a column in LDS at most (odd)
+static_assert(kPackRleMaxH % 64 == 0 && 64 * kColWords * 8 <= 64 * 1024, "the strip fits the static LDS of a workgroup");
+
+__device__ __forceinline__ int64_t run_at(const int32_t* __restrict__ counts, int64_t i, int64_t total) {
+  const int c = i < total ? counts[i] : 0;
+  return c < 0 ? 0 : c;                                    // a negative run (malformed input) counts as empty
+}
+
+__global__ void __launch_bounds__(kBlock)
+run_chunk_sums_kernel(const int32_t* __restrict__ counts, int64_t total, int64_t* __restrict__ chunk_sum) {
+  __shared__ int64_t wave_tot[kWaves];
+  const int64_t i0 = static_cast<int64_t>(blockIdx.x) * kRunChunk + static_cast<int64_t>(threadIdx.x) * kRunPer;
+  int64_t s = 0;
+#pragma unroll
+  for (int j = 0; j < kRunPer; ++j) s += run_at(counts, i0 + j, total);
+  int64_t all;
+  block_scan<kBlock>(s, wave_tot, all);
+  if (threadIdx.x == 0) chunk_sum[blockIdx.x] = all;
+}
+
+__global__ void __launch_bounds__(kBlock) run_chunk_offsets_kernel(int64_t nchunks, int64_t* __restrict__ chunk_sum) {
+  __shared__ int64_t wave_tot[kWaves];
+  scan_tiles<kBlock>(
+      nchunks, [&](int64_t b) { return chunk_sum[b]; }, [&](int64_t b, int64_t before) { chunk_sum[b] = before; }, wave_tot);
+}
+
+__global__ void __launch_bounds__(kBlock)
+run_starts_kernel(const int32_t* __restrict__ counts, int64_t total, const int64_t* __restrict__ chunk_base,
+                  int64_t* __restrict__ start) {
+  __shared__ int64_t wave_tot[kWaves];
+  const int64_t i0 = static_cast<int64_t>(blockIdx.x) * kRunChunk + static_cast<int64_t>(threadIdx.x) * kRunPer;
+  int64_t c[kRunPer], s = 0;
+#pragma unroll
+  for (int j = 0; j < kRunPer; ++j) s += c[j] = run_at(counts, i0 + j, total);
+  int64_t all;
+  int64_t at = chunk_base[blockIdx.x] + block_scan<kBlock>(s, wave_tot, all) - s;
+#pragma unroll
+  for (int j = 0; j < kRunPer; ++j) {
+    if (i0 + j < total) start[i0 + j] = at;
+    at += c[j];
+  }
+}
+
+// bits [a, b) of a word, 0 <= a < b <= 64
+__device__ __forceinline__ detops_u64 bit_range(int a, int b) {
+  return (b >= 64 ? ~0ull : (1ull << b) - 1) & ~((1ull << a) - 1);
+}
+
+__global__ void __launch_bounds__(kBlock)
+mask_pack_rle_kernel(const int32_t* __restrict__ counts, const int64_t* __restrict__ run_offset,
+                     const int64_t* __restrict__ start, int64_t total, const int32_t* __restrict__ plane_hw, int plane_base,
+                     const int64_t* __restrict__ word_offset, detops_u64* __restrict__ words, int32_t* __restrict__ area,
+                     int32_t* __restrict__ extent) {
+  __shared__ detops_u64 col[64 * kColWords];
+  const int n = plane_base + blockIdx.y;
+  const int H = plane_hw[2 * n], W = plane_hw[2 * n + 1];
+  if (H <= 0 || W <= 0 || H > kPackRleMaxH) return;     // (the entry point refuses a call with a taller plane)
+  const int WW = (W + 63) / 64, HW = (H + 63) / 64, HWp = HW | 1;
+  int64_t r0 = run_offset[n], r1 = run_offset[n + 1];
+  r0 = r0 < 0 ? 0 : (r0 > total ? total : r0);
+  r1 = r1 < r0 ? r0 : (r1 > total ? total : r1);
+  const int nr = static_cast<int>(r1 - r0 > INT32_MAX ? INT32_MAX : r1 - r0);
+  const int64_t* st = start + r0;
+  const int32_t* rc = counts + r0;
+  const int64_t base = nr ? st[0] : 0;
+  detops_u64* dst = words + word_offset[n];
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  int count = 0, rmin = H, rmax = -1, cmin = WW, cmax = -1;
+  for (int s = blockIdx.x; s < WW; s += gridDim.x) {
+    const int x0 = s * 64, ncol = min(64, W - x0);
+    for (int idx = threadIdx.x; idx < ncol * HW; idx += kBlock) {
+      const int c = idx / HW, r = idx % HW;
+      const int64_t lo = static_cast<int64_t>(x0 + c) * H + r * 64;        // positions of the mask this word holds
+      const int64_t hi = lo + min(64, H - r * 64);
+      detops_u64 word = 0;
+      if (nr) {
+        for (int j = last_at_or_below(st, nr, base + lo); j < nr; ++j) {
+          const int64_t a = st[j] - base;
+          if (a >= hi) break;
+          const int64_t b = a + (rc[j] < 0 ? 0 : rc[j]);
+          if ((j & 1) && b > lo && b > a)
+            word |= bit_range(static_cast<int>((a < lo ? lo : a) - lo), static_cast<int>((b > hi ? hi : b) - lo));
+        }
+      }
+      col[c * HWp + r] = word;
+    }
+    __syncthreads();
+    for (int r = wave; r < HW; r += kWaves) {
+      const detops_u64 v = lane < ncol ? col[lane * HWp + r] : 0;
+      detops_u64 mine = 0;
+#pragma unroll 8
+      for (int b = 0; b < 64; ++b) {
+        const detops_u64 word = __ballot((v >> b) & 1);                     // row 64 r + b of the strip
+        if (word) {                                                        // wave-uniform
+          count += __popcll(word);
+          rmin = min(rmin, r * 64 + b);
+          rmax = max(rmax, r * 64 + b);
+          cmin = min(cmin, s);
+          cmax = max(cmax, s);
+        }
+        if (lane == b) mine = word;
+      }
+      const int y = r * 64 + lane;
+      if (y < H) dst[static_cast<int64_t>(y) * WW + s] = mine;
+    }
+    __syncthreads();
+  }
+  if (lane == 0 && count > 0) {                    // integer atomics: the result does not depend on their order
+    atomicAdd(&area[n], count);
+    atomicMin(&extent[4 * n + 0], rmin);
+    atomicMax(&extent[4 * n + 1], rmax);
+    atomicMin(&extent[4 * n + 2], cmin);
+    atomicMax(&extent[4 * n + 3], cmax);
+  }
+}
+
+int64_t run_chunks_of(int64_t total) { return (total + kRunChunk - 1) / kRunChunk; }
 
 // ---------------------------------------------------------------------------------------------------- pair counts
 // One wave per pair.  The words of the two planes inside the intersection of their extents, 64 per step.
@@ -363,6 +497,45 @@ DETOPS_API int detops_mask_pack(const unsigned char* planes, const int64_t* plan
     hipLaunchKernelGGL(mask_pack_kernel, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(ny)), dim3(kBlock), 0,
                        as_stream(stream), planes, plane_offset, plane_hw, base, word_offset,
                        reinterpret_cast<detops_u64*>(words), area, extent);
+  }
+  return launch_status();
+}
+
+DETOPS_API size_t detops_mask_pack_rle_workspace_bytes(int64_t total) {
+  if (total <= 0) return 0;
+  return static_cast<size_t>(total + run_chunks_of(total)) * sizeof(int64_t);
+}
+
+DETOPS_API int detops_mask_pack_rle(const int32_t* counts, const int64_t* run_offset, int64_t total, const int32_t* plane_hw,
+                                    int N, int max_h, int max_w, const int64_t* word_offset, uint64_t* words, int32_t* area,
+                                    int32_t* extent, void* workspace, size_t workspace_bytes, detops_stream_t stream) {
+  if (N < 0 || total < 0 || max_h < 0 || max_w < 0 || run_chunks_of(total) > INT32_MAX) return DETOPS_EINVAL;
+  if (N == 0) return 0;
+  if (max_h > kPackRleMaxH) return DETOPS_EUNSUPPORTED;
+  const bool pixels = max_h > 0 && max_w > 0;
+  if (!run_offset || !plane_hw || !word_offset || !area || !extent || (pixels && !words) ||
+      (total > 0 && (!counts || !workspace)))
+    return DETOPS_EINVAL;
+  if (workspace_bytes < detops_mask_pack_rle_workspace_bytes(total)) return DETOPS_EWORKSPACE;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(mask_pack_init_kernel, dim3(static_cast<unsigned>((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                     plane_hw, N, area, extent);
+  if (!pixels) return launch_status();
+  int64_t* start = static_cast<int64_t*>(workspace);
+  if (total > 0) {
+    const int64_t nchunks = run_chunks_of(total);
+    int64_t* chunk_sum = start + total;
+    const dim3 grid(static_cast<unsigned>(nchunks));
+    hipLaunchKernelGGL(run_chunk_sums_kernel, grid, dim3(kBlock), 0, st, counts, total, chunk_sum);
+    hipLaunchKernelGGL(run_chunk_offsets_kernel, dim3(1), dim3(kBlock), 0, st, nchunks, chunk_sum);
+    hipLaunchKernelGGL(run_starts_kernel, grid, dim3(kBlock), 0, st, counts, total, chunk_sum, start);
+  }
+  const int strips = (max_w + 63) / 64;
+  const unsigned gx = static_cast<unsigned>(strips < 1 ? 1 : (strips > 4096 ? 4096 : strips));
+  for (int base = 0; base < N; base += 65535) {
+    const int ny = N - base < 65535 ? N - base : 65535;
+    hipLaunchKernelGGL(mask_pack_rle_kernel, dim3(gx, static_cast<unsigned>(ny)), dim3(kBlock), 0, st, counts, run_offset,
+                       start, total, plane_hw, base, word_offset, reinterpret_cast<detops_u64*>(words), area, extent);
   }
   return launch_status();
 }

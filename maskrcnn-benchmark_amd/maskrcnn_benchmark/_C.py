@@ -803,6 +803,84 @@ def rle_string_list(data, byte_offset):
     return _rle_cpu.to_str_list(data.numpy(), byte_offset.numpy())
 
 
+def _hw_arg(name, hw, N, device):
+    if hw is None:
+        return None
+    hw = torch.as_tensor(hw, dtype=torch.int32).reshape(-1, 2)
+    if hw.shape[0] != N:
+        raise ValueError("%s: hw must be [N, 2] for N = %d masks, got %s" % (name, N, tuple(hw.shape)))
+    return hw.to(device).contiguous()
+
+
+def rle_string_decode_status(data, byte_offset, hw=None):
+    """rle_string_decode without the check: -> (counts, run_offset, status int32 [N]); a flagged mask's runs are unspecified
+    but in bounds (include/detops.h, "Reading compressed RLE strings": the DETOPS_RLE_* bits)."""
+    if data.dtype != torch.uint8 or byte_offset.dtype != torch.int64 or data.dim() != 1 or byte_offset.dim() != 1 \
+            or byte_offset.numel() < 1:
+        raise ValueError("rle_string_decode: expected bytes uint8 [B] and byte_offset int64 [N + 1]")
+    if data.device != byte_offset.device:
+        raise ValueError("rle_string_decode: bytes and byte_offset live on different devices")
+    B, N = data.numel(), byte_offset.numel() - 1
+    hw = _hw_arg("rle_string_decode", hw, N, data.device)
+    if not data.is_cuda:
+        counts, run_offset, status = _rle_cpu.rle_decode(data.numpy(), byte_offset.numpy(), None if hw is None else hw.numpy())
+        return torch.from_numpy(counts), torch.from_numpy(run_offset), torch.from_numpy(status)
+    data, byte_offset = data.contiguous(), byte_offset.contiguous()
+    dev = data.device
+    run_offset = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+    if N == 0 or B == 0:        # only empty strings: nothing to launch; an empty string holds no pixel
+        status = torch.zeros((N,), dtype=torch.int32, device=dev)
+        if hw is not None:
+            status = ((hw[:, 0].to(torch.int64) * hw[:, 1]) != 0).to(torch.int32) * _rle_cpu.BAD_SUM
+        return torch.empty((0,), dtype=torch.int32, device=dev), run_offset, status
+    nbytes = int(lib.detops_rle_decode_workspace_bytes(B, N))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    status = torch.empty((N,), dtype=torch.int32, device=dev)
+    with _on_device(data):
+        with _timed(("rle_decode_count[N=%d,bytes=%d]", (N, B)), data):
+            check(lib.detops_rle_decode_count(ptr(data), ptr(byte_offset), B, N, ptr(run_offset), ptr(ws), nbytes,
+                                              stream_of(data)), "rle_decode_count")
+        ends = torch.stack([byte_offset[0], byte_offset[-1], run_offset[-1], (byte_offset[1:] < byte_offset[:-1]).sum()]).tolist()
+        if ends[0] != 0 or ends[1] != B or ends[3] != 0:     # (the kernels stay in bounds either way; the runs would mean nothing)
+            raise ValueError("rle_string_decode: byte_offset must start at 0, not decrease and end at len(bytes)")
+        total = int(ends[2])
+        counts = torch.empty((total,), dtype=torch.int32, device=dev)
+        with _timed(("rle_decode_write[N=%d,bytes=%d]", (N, B)), data):
+            check(lib.detops_rle_decode_write(ptr(data), ptr(byte_offset), B, N, ptr(run_offset), total, ptr(hw), ptr(counts),
+                                              ptr(status), ptr(ws), nbytes, stream_of(data)), "rle_decode_write")
+    return counts, run_offset, status
+
+
+def rle_string_decode(data, byte_offset, hw=None):
+    """Compressed COCO `counts` strings back to uncompressed runs: the inverse of rle_strings (extension; include/detops.h:
+    "Reading compressed RLE strings", detops_rle_decode_count / _write).  bytes uint8 [B] and byte_offset int64 [N + 1] (mask
+    n's string is bytes[byte_offset[n]:byte_offset[n + 1]]); hw [N, 2] (H, W), when given, must be what each mask's runs
+    sum to.  -> (counts int32 [total], run_offset int64 [N + 1]) on the inputs' device.  Malformed input raises a
+    ValueError that names the first flagged mask and its status bits (one more host read).  CPU tensors take the numpy
+    statement of the same definition (_rle_cpu.py)."""
+    counts, run_offset, status = rle_string_decode_status(data, byte_offset, hw)
+    err = _rle_cpu.status_error(status.cpu().numpy())
+    if err is not None:
+        raise err
+    return counts, run_offset
+
+
+def rle_string_decode_list(strings, hw=None, device=None):
+    """rle_string_decode for a list of N str, as a result file holds them; the result lives on `device` (default: the
+    CPU).  The mirror of rle_string_list: ONE host-to-device copy, the offsets (and hw) in front of the bytes."""
+    data, byte_offset = _rle_cpu.from_str_list(list(strings))
+    N = byte_offset.size - 1
+    device = torch.device("cpu" if device is None else device)
+    if device.type != "cuda":
+        return rle_string_decode(torch.from_numpy(data.copy()), torch.from_numpy(byte_offset), hw)
+    hw_h = np.zeros((0, 2), np.int32) if hw is None else _hw_arg("rle_string_decode_list", hw, N, "cpu").numpy()
+    host = np.concatenate([byte_offset.view(np.uint8), hw_h.reshape(-1).view(np.uint8), data])
+    both = torch.from_numpy(host).to(device)
+    n8, h8 = byte_offset.size * 8, hw_h.size * 4
+    return rle_string_decode(both[n8 + h8:], both[:n8].view(torch.int64),
+                             None if hw is None else both[n8:n8 + h8].view(torch.int32).reshape(-1, 2))
+
+
 # ------------------------------------------------------------------------------------------ target assignment
 def match_boxes(gt_boxes, gt_valid, boxes, high_threshold, low_threshold, allow_low_quality_matches):
     """Fused IoU + Matcher (extension; reference structures/boxlist_ops.py:53-89 + modeling/matcher.py:42-112):
@@ -1137,6 +1215,47 @@ def mask_pack(planes):
                                            word_offset[a:b].data_ptr(), ptr(words), area[a:b].data_ptr(),
                                            extent[a:b].data_ptr(), stream_of(words)), "mask_pack")
     return words, word_offset, hw, area, extent
+
+
+MASK_PACK_RLE_MAX_H = _lib._abi.MASK_PACK_RLE_MAX_H
+
+
+def mask_pack_rle(counts, run_offset, hw):
+    """mask_pack from uncompressed RLE, no plane stored (extension; include/detops.h: detops_mask_pack_rle).  counts int32
+    [total] and run_offset int64 [N + 1] as paste_masks_rle or rle_string_decode make them (column-major runs starting
+    with a 0-run), hw [N, 2] (H, W) per mask -> the five tensors of mask_pack.  A call with a plane taller than
+    MASK_PACK_RLE_MAX_H, and CPU tensors, take the numpy implementation (_eval_cpu.py)."""
+    if counts.dtype != torch.int32 or run_offset.dtype != torch.int64 or counts.dim() != 1 or run_offset.dim() != 1 \
+            or run_offset.numel() < 1:
+        raise ValueError("mask_pack_rle: expected counts int32 [total] and run_offset int64 [N + 1]")
+    if counts.device != run_offset.device:
+        raise ValueError("mask_pack_rle: counts and run_offset live on different devices")
+    N, total, dev = run_offset.numel() - 1, counts.numel(), counts.device
+    hw_h = torch.as_tensor(hw).detach().cpu().to(torch.int32).reshape(-1, 2)
+    if hw_h.shape[0] != N or (N and (int(hw_h.min()) < 0 or int((hw_h[:, 0].long() * hw_h[:, 1].long()).max()) >= 2 ** 31)):
+        raise ValueError("mask_pack_rle: hw must be [N, 2] sizes of fewer than 2^31 pixels for N = %d masks" % N)
+    max_h, max_w = (int(hw_h[:, 0].max()), int(hw_h[:, 1].max())) if N else (0, 0)
+    if not counts.is_cuda or max_h > MASK_PACK_RLE_MAX_H:
+        w, off, hw_o, area, ext = _eval_cpu.mask_pack_rle(_np(counts), _np(run_offset), hw_h.numpy())
+        return tuple(torch.from_numpy(a).to(dev) for a in (w.view(np.int64), off, hw_o, area, ext))
+    counts, run_offset = counts.contiguous(), run_offset.contiguous()
+    per = hw_h[:, 0].to(torch.int64) * ((hw_h[:, 1].to(torch.int64) + 63) // 64)
+    ends = torch.cumsum(per, 0)
+    n_words = int(ends[-1]) if N else 0
+    words = torch.empty((n_words,), dtype=torch.int64, device=dev)
+    area = torch.empty((N,), dtype=torch.int32, device=dev)
+    extent = torch.empty((N, 4), dtype=torch.int32, device=dev)
+    # one host-to-device copy: the word offsets in front of the sizes
+    both = torch.cat([(ends - per).view(torch.int32), hw_h.reshape(-1)]).to(dev)
+    word_offset, hw_d = both[:2 * N].view(torch.int64), both[2 * N:].reshape(N, 2)
+    if N:
+        nbytes = int(lib.detops_mask_pack_rle_workspace_bytes(total))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        with _on_device(counts), _timed(("mask_pack_rle[N=%d,runs=%d]", (N, total)), counts):
+            check(lib.detops_mask_pack_rle(ptr(counts), ptr(run_offset), total, ptr(hw_d), N, max_h, max_w, ptr(word_offset),
+                                           ptr(words), ptr(area), ptr(extent), ptr(ws), nbytes, stream_of(counts)),
+                  "mask_pack_rle")
+    return words, word_offset, hw_d, area, extent
 
 
 def mask_pair_counts(dt_pack, gt_pack, dt_offset, gt_offset, iou_offset, total_pairs):

@@ -13,6 +13,12 @@ ERRORS = {-1: "DETOPS_EINVAL (bad shape / null pointer)", -2: "DETOPS_EWORKSPACE
 
 F32, F16, BF16 = 0, 1, 2  # DETOPS_F32 / DETOPS_F16 / DETOPS_BF16
 
+# DETOPS_RLE_*: the per-mask status bits of detops_rle_decode_write, lowest bit first
+RLE_STATUS = {1: "DETOPS_RLE_BAD_BYTE (a byte outside 48..111)", 2: "DETOPS_RLE_TRUNCATED (the last byte continues)",
+              4: "DETOPS_RLE_LONG_VALUE (a value of more than 7 bytes)", 8: "DETOPS_RLE_BAD_RUN (a run outside [0, 2^31))",
+              16: "DETOPS_RLE_BAD_SUM (the runs do not sum to h * w)"}
+MASK_PACK_RLE_MAX_H = 4096  # DETOPS_MASK_PACK_RLE_MAX_H
+
 # the fields of struct DetopsTuning (csrc/detops_common.h) = the keys of detops_tuning_set / detops_tuning_get
 TUNING_KEYS = ("roi_bwd_impl", "roi_bwd_seg", "nms_fault", "nms_spin_budget", "roi_bwd_ring", "roi_bwd_ct", "roi_bwd_split",
                "roi_bwd_maxseg", "roi_bwd_extras", "roi_bwd_groups", "roi_bwd_scan_ct", "roi_bwd_debug", "roi_fwd_impl",
@@ -76,6 +82,9 @@ SIGNATURES = {
     "detops_rle_string_workspace_bytes": (c_size_t, [ctypes.c_int64]),
     "detops_rle_string_count": (c_int, [_P, _P, ctypes.c_int64, c_int, _P, _P, c_size_t, _P]),
     "detops_rle_string_write": (c_int, [_P, _P, ctypes.c_int64, c_int, _P, _P, _P, c_size_t, _P]),
+    "detops_rle_decode_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int]),
+    "detops_rle_decode_count": (c_int, [_P, _P, ctypes.c_int64, c_int, _P, _P, c_size_t, _P]),
+    "detops_rle_decode_write": (c_int, [_P, _P, ctypes.c_int64, c_int, _P, ctypes.c_int64, _P, _P, _P, _P, c_size_t, _P]),
     "detops_polygon_mask_targets": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
     "detops_polygons_to_masks": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P]),
     "detops_image_batch_u8": (c_int, [_P, ctypes.c_int64, _P, _P, _P, c_int, _P] + [c_int] * 4 + [_P, _P]),
@@ -83,6 +92,8 @@ SIGNATURES = {
     "detops_bbox_aug_merge_count": (c_int, [_P, _P, _P] + [c_int] * 4 + [c_float, _P, _P, _P, c_size_t, _P]),
     "detops_bbox_aug_merge_write": (c_int, [_P] * 6 + [c_int] * 4 + [c_float, _P, ctypes.c_int64, _P, _P, _P, c_size_t, _P]),
     "detops_mask_pack": (c_int, [_P, _P, _P, c_int, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    "detops_mask_pack_rle_workspace_bytes": (c_size_t, [ctypes.c_int64]),
+    "detops_mask_pack_rle": (c_int, [_P, _P, ctypes.c_int64, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "detops_mask_pair_counts": (c_int, [_P] * 11 + [c_int, ctypes.c_int64, _P, _P]),
     "detops_eval_iou": (c_int, [c_int] + [_P] * 9 + [c_int, ctypes.c_int64, _P, _P]),
     "detops_eval_match": (c_int, [c_int] + [_P] * 4 + [c_int, ctypes.c_int64, ctypes.c_int64, c_int] + [_P] * 4

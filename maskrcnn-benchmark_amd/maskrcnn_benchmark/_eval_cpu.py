@@ -44,6 +44,27 @@ def mask_pack(planes):
             np.array(extent, np.int32).reshape(-1, 4))
 
 
+def mask_pack_rle(counts, run_offset, hw):
+    """mask_pack of the planes that uncompressed RLE describes (detops_mask_pack_rle): counts int32 [total], run_offset
+    int64 [N + 1], hw [N, 2].  Runs are column-major and start with a 0-run, so pixel (y, x) is set iff position x * H + y
+    lies in an odd-indexed run; zero-length runs only toggle; positions beyond the runs are 0, runs beyond H * W and
+    negative runs are ignored.  One plane at a time is laid out on the host."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    ro = np.asarray(run_offset, dtype=np.int64).reshape(-1)
+    hw = np.asarray(hw, dtype=np.int64).reshape(-1, 2)
+    if ro.size != hw.shape[0] + 1 or ro[0] != 0 or ro[-1] != c.size or (np.diff(ro) < 0).any():
+        raise ValueError("mask_pack_rle: run_offset must hold N + 1 entries, start at 0, not decrease and end at len(counts)")
+    planes = []
+    for n in range(hw.shape[0]):
+        H, W = int(hw[n, 0]), int(hw[n, 1])
+        ends = np.minimum(np.cumsum(np.maximum(c[ro[n]:ro[n + 1]], 0)), H * W)
+        runs = np.diff(np.concatenate([np.zeros(1, np.int64), ends]))
+        flat = np.repeat((np.arange(runs.size) & 1).astype(np.uint8), runs)
+        flat = np.concatenate([flat, np.zeros(H * W - flat.size, np.uint8)])
+        planes.append(flat.reshape(W, H).T[None])
+    return mask_pack(planes)
+
+
 def _pairs(dt_offset, gt_offset, iou_offset):
     """-> (d, g) index arrays [total_pairs] into the sorted detections / ground truths"""
     P = len(dt_offset) - 1

@@ -52,6 +52,24 @@ def rle_to_mask(rle):
     return torch.repeat_interleave(values, runs).reshape(w, h).t().contiguous()
 
 
+def decode_rle(rle):
+    """a COCO RLE {"size": [h, w], "counts": ...} -> uint8 [h, w].  `counts` is an uncompressed list (rle_to_mask) or the
+    COMPRESSED string every converter built on pycocotools' encode writes: that goes through _C.rle_string_decode_list
+    (include/detops.h, "Reading compressed RLE strings"); a malformed string, or runs that do not sum to h * w, raise
+    ValueError."""
+    counts = rle["counts"]
+    if isinstance(counts, (list, tuple)):
+        return rle_to_mask(rle)
+    from maskrcnn_benchmark import _C
+
+    h, w = (int(v) for v in rle["size"])
+    if isinstance(counts, bytes):
+        counts = counts.decode("latin-1")
+    runs, _ = _C.rle_string_decode_list([counts], [(h, w)])
+    values = (torch.arange(runs.numel()) % 2).to(torch.uint8)
+    return torch.repeat_interleave(values, runs.to(torch.int64)).reshape(w, h).t().contiguous()
+
+
 class COCODataset(torch.utils.data.Dataset):
     evaluation_style = "coco"
 
@@ -119,7 +137,7 @@ class COCODataset(torch.utils.data.Dataset):
         segs = [obj.get("segmentation") for obj in anno]
         if anno and all(s is not None for s in segs):
             if any(isinstance(s, dict) for s in segs):         # a crowd's RLE: the image's masks as planes
-                planes = [rle_to_mask(s) if isinstance(s, dict)
+                planes = [decode_rle(s) if isinstance(s, dict)
                           else SegmentationMask([s], size, mode="poly").get_mask_tensor().reshape(size[1], size[0]).to(torch.uint8)
                           for s in segs]
                 for s, p in zip(segs, planes):

@@ -15,14 +15,21 @@ Masker(0.5, padding=1)'s parameters: device tensors by `_C.paste_masks_rle` (pla
 `_C.rle_strings` (include/detops.h, "Compressed RLE strings"), so one image leaves the device as boxes, scores, labels,
 keypoints, the strings' bytes and their offsets.
 
-Not built: reading result files back, decoding compressed strings, `box_only` proposals, OKS."""
+Reading them back: `load_results` turns `bbox.json` / `segm.json` (this project's or another tool's) into the BoxLists the
+evaluator takes, the masks as RLEMasks decoded by `_C.rle_string_decode_list` (include/detops.h, "Reading compressed RLE
+strings"); `evaluate_result_files` scores the files against a dataset's ground truth (tools/evaluate_results.py).
+
+Not built: `box_only` proposals, OKS (so `keypoints.json` is written but cannot be scored)."""
 import json
 import os
 
+import numpy as np
 import torch
 
-from maskrcnn_benchmark import _C
+from maskrcnn_benchmark import _C, _rle_cpu
 from maskrcnn_benchmark.modeling.roi_heads.mask_head.inference import paste_masks_torch
+from maskrcnn_benchmark.structures.bounding_box import BoxList
+from maskrcnn_benchmark.structures.rle_masks import RLEMasks
 
 IOU_TYPES = ("bbox", "segm", "keypoints")
 MASK_THRESHOLD, MASK_PADDING = 0.5, 1      # the reference's Masker(threshold=0.5, padding=1)
@@ -146,6 +153,129 @@ def prepare_for_coco_segmentation(predictions, dataset):
 
 def prepare_for_coco_keypoint(predictions, dataset):
     return _prepare("keypoints", predictions, dataset)
+
+
+# ------------------------------------------------------------------------------------------------ reading them back
+def _read_entries(path_or_list):
+    if isinstance(path_or_list, (str, bytes, os.PathLike)):
+        with open(path_or_list) as f:
+            path_or_list = json.load(f)
+    if not isinstance(path_or_list, list):
+        raise ValueError("a result file holds a list of entries, got %s" % type(path_or_list).__name__)
+    return path_or_list
+
+
+def _segmentation_string(entry, height, width):
+    """the entry's `segmentation` as a compressed string; an uncompressed counts list is coded by the numpy coder, so that
+    one decode call checks and unpacks every mask of the file alike"""
+    seg = entry.get("segmentation")
+    if not isinstance(seg, dict) or "counts" not in seg or "size" not in seg:
+        raise ValueError("result files: a segmentation must be an RLE {size, counts}; polygons are not read (image %r)"
+                         % (entry.get("image_id"),))
+    if [int(v) for v in seg["size"]] != [height, width]:
+        raise ValueError("result files: an RLE of size %s for image %r of %d x %d" % (seg["size"], entry["image_id"], height, width))
+    counts = seg["counts"]
+    if isinstance(counts, bytes):
+        counts = counts.decode("latin-1")
+    if isinstance(counts, str):
+        return counts
+    runs = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if runs.size and (runs.min() < 0 or runs.max() >= 2 ** 31):
+        raise ValueError("result files: uncompressed counts outside [0, 2^31) (image %r)" % (entry["image_id"],))
+    return _rle_cpu.to_str_list(*_rle_cpu.rle_strings(runs.astype(np.int32), np.array([0, runs.size])))[0]
+
+
+def load_results(path_or_list, dataset, iou_type, device=None):
+    """A `bbox.json` / `segm.json` result file (a path, or its list of entries) -> a list of BoxList in dataset order, what
+    COCOStyleEvaluator.update takes: the inverse of the writer.  Entries are grouped by `image_id` through the inverse of
+    `id_to_img_map` and keep the file's order inside an image (the evaluator's stable sort then reproduces ties); labels
+    come through `json_category_id_to_contiguous_id`; a dataset without these maps uses the index and the label, as the
+    writer does.  `bbox` goes from xywh through BoxList(mode="xywh").convert("xyxy"); a segm entry without `bbox` gets the
+    full-image box, which the segm rules never read.  `segmentation` is a compressed string or an uncompressed list and
+    becomes the `mask` field, an RLEMasks on `device` (every string of the file in ONE _C.rle_string_decode_list call).
+    ValueError: an unknown image id or category id, a polygon, an RLE of another size than its image, malformed strings."""
+    if iou_type == "keypoints":
+        raise NotImplementedError("reading keypoints.json for scoring (OKS) is not built")
+    if iou_type not in ("bbox", "segm"):
+        raise ValueError("load_results: unknown iou type %r" % (iou_type,))
+    entries = _read_entries(path_or_list)
+    ids = getattr(dataset, "id_to_img_map", None)
+    index_of = {v: k for k, v in ids.items()} if ids is not None else None
+    labels_of = getattr(dataset, "json_category_id_to_contiguous_id", None)
+    if labels_of is None and getattr(dataset, "contiguous_category_id_to_json_id", None) is not None:
+        labels_of = {v: k for k, v in dataset.contiguous_category_id_to_json_id.items()}
+    per_image = [[] for _ in range(len(dataset))]
+    for e in entries:
+        image_id = e["image_id"]
+        index = index_of.get(image_id) if index_of is not None else (image_id if isinstance(image_id, int) else None)
+        if index is None or not 0 <= index < len(per_image):
+            raise ValueError("result files: image_id %r is not in the dataset" % (image_id,))
+        if labels_of is not None and e["category_id"] not in labels_of:
+            raise ValueError("result files: category_id %r is not in the dataset" % (e["category_id"],))
+        per_image[index].append(e)
+    device = torch.device("cpu" if device is None else device)
+    sizes = []
+    for index in range(len(per_image)):
+        info = dataset.get_img_info(index)
+        sizes.append((int(info["width"]), int(info["height"])))
+    rle = None
+    if iou_type == "segm":
+        strings = [_segmentation_string(e, sizes[i][1], sizes[i][0]) for i, es in enumerate(per_image) for e in es]
+        hw = [(sizes[i][1], sizes[i][0]) for i, es in enumerate(per_image) for _ in es]
+        rle = _C.rle_string_decode_list(strings, hw, device)
+        starts = rle[1].tolist()                     # one host read for the whole file
+    out, first = [], 0
+    for index, es in enumerate(per_image):
+        W, H = sizes[index]
+        if es and all("bbox" in e for e in es):
+            boxes = torch.tensor([e["bbox"] for e in es], dtype=torch.float32).reshape(-1, 4)
+            boxlist = BoxList(boxes, (W, H), mode="xywh").convert("xyxy")
+        elif iou_type == "bbox" and es:
+            raise ValueError("result files: a bbox entry without `bbox` (image %r)" % (es[0]["image_id"],))
+        else:
+            boxlist = BoxList(torch.tensor([[0.0, 0.0, W - 1.0, H - 1.0]] * len(es)).reshape(-1, 4), (W, H), mode="xyxy")
+        boxlist.add_field("scores", torch.tensor([e["score"] for e in es], dtype=torch.float32))
+        cats = [e["category_id"] for e in es]
+        boxlist.add_field("labels", torch.tensor(cats if labels_of is None else [labels_of[c] for c in cats], dtype=torch.int64))
+        boxlist = boxlist.to(device)
+        if rle is not None:                          # the image's slice of the file's runs
+            a, b = starts[first], starts[first + len(es)]
+            boxlist.add_field("mask", RLEMasks(rle[0][a:b], rle[1][first:first + len(es) + 1] - a, (W, H)))
+        out.append(boxlist)
+        first += len(es)
+    return out
+
+
+def evaluate_result_files(dataset, files, output_folder=None, batch=8, device="cpu", expected_results=(),
+                          expected_results_sigma_tol=4):
+    """Score saved result files against `dataset`'s ground truth: files = {"bbox": path, "segm": path} (either or both; a
+    list of entries serves as a path).  One COCOStyleEvaluator per file, fed `batch` images at a time on `device`; the
+    masks of segm.json go from runs to bit rows there (_C.mask_pack_rle), no plane is laid out.  -> the COCOResults of
+    finish_coco, which also logs the tables and, with `output_folder`, writes coco_results.pth / coco_results.txt.
+    `keypoints` raises NotImplementedError: OKS is not built."""
+    from . import COCOStyleEvaluator, _groundtruth, finish_coco
+
+    if "keypoints" in files:
+        raise NotImplementedError("the keypoints IoU type (OKS) is not built: keypoints.json cannot be scored")
+    iou_types = tuple(t for t in ("bbox", "segm") if t in files)
+    unknown = sorted(set(files) - set(iou_types))
+    if unknown or not iou_types:
+        raise ValueError("evaluate_result_files: expected files for bbox and / or segm, got %s" % sorted(files))
+    num_classes = getattr(dataset, "num_classes", None) or 81
+    device = torch.device(device)
+    merged = COCOStyleEvaluator(iou_types, num_classes)
+    for t in iou_types:
+        predictions = load_results(files[t], dataset, t, device)
+        evaluator = COCOStyleEvaluator((t,), num_classes)
+        for i in range(0, len(predictions), batch):
+            preds = predictions[i:i + batch]
+            evaluator.update(preds, [_groundtruth(dataset, j).to(device) for j in range(i, i + len(preds))])
+        merged.records[t] = evaluator.records[t]
+        merged.num_images, merged.num_groundtruths = evaluator.num_images, evaluator.num_groundtruths
+        merged.num_detections = max(merged.num_detections, evaluator.num_detections)
+    if output_folder:
+        os.makedirs(output_folder, exist_ok=True)
+    return finish_coco(merged, output_folder, expected_results, expected_results_sigma_tol)
 
 
 class COCOResultsWriter(object):

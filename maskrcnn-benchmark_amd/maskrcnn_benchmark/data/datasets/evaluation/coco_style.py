@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from maskrcnn_benchmark import _C
+from maskrcnn_benchmark.structures.rle_masks import RLEMasks
 from maskrcnn_benchmark.structures.segmentation_mask import SegmentationMask
 
 IOU_THRS = np.linspace(0.5, 0.95, 10)
@@ -55,8 +56,37 @@ def build_problems(dt_img, dt_label, dt_score, gt_img, gt_label, num_classes, ma
             "counts_host": (int(D_h.sum()), int(G_h.sum()), int(G_h.max()) if P else 0)}
 
 
+def _pack_masks(per_image):
+    """per image a [n, H, W] uint8 / bool tensor or an RLEMasks -> the five tensors of _C.mask_pack over all of them, in
+    order.  Dense planes alone are one _C.mask_pack call, as ever; runs go to _C.mask_pack_rle (consecutive RLE images
+    share a call) and the packs are joined."""
+    if not any(isinstance(m, RLEMasks) for m in per_image):
+        return _C.mask_pack(per_image)
+    packs, i = [], 0
+    while i < len(per_image):
+        rle, j = isinstance(per_image[i], RLEMasks), i
+        while j < len(per_image) and isinstance(per_image[j], RLEMasks) == rle:
+            j += 1
+        if rle:
+            seg, base, offsets = per_image[i:j], 0, [per_image[i].run_offset[:1]]
+            for m in seg:
+                offsets.append(m.run_offset[1:] + base)
+                base += m.counts.numel()
+            packs.append(_C.mask_pack_rle(torch.cat([m.counts for m in seg]), torch.cat(offsets), [hw for m in seg for hw in m.hw()]))
+        else:
+            packs.append(_C.mask_pack(per_image[i:j]))
+        i = j
+    sizes = [int(p[0].numel()) for p in packs]
+    word_offset = torch.cat([p[1] + sum(sizes[:k]) for k, p in enumerate(packs)])
+    return (torch.cat([p[0] for p in packs]), word_offset) + tuple(torch.cat([p[k] for p in packs]) for k in (2, 3, 4))
+
+
 def _planes_of_target(target):
     masks = target.get_field("masks")
+    if isinstance(masks, RLEMasks):
+        if tuple(masks.size) != tuple(target.size):
+            raise ValueError("ground-truth RLE masks of an image of %s for an image of %s" % (masks.size, tuple(target.size)))
+        return masks.to(target.bbox.device)
     if isinstance(masks, SegmentationMask):
         masks = masks.convert("mask").instances.masks
     if masks.dim() == 2:
@@ -92,8 +122,9 @@ class COCOStyleEvaluator(object):
     def update(self, predictions, targets):
         """predictions, targets: two lists of BoxList (one per image), on the device or the CPU.  Predictions carry
         `scores`, `labels` and, for segm, `mask`: dense bool planes [n, 1, H, W] of the image's size, or probabilities
-        [n, 1, M, M], which Masker(threshold=0.5, padding=1) pastes.  Targets carry `labels` and may carry `masks`
-        (either SegmentationMask mode), `iscrowd` and `area`."""
+        [n, 1, M, M], which Masker(threshold=0.5, padding=1) pastes, or an RLEMasks (the runs of a result file), which goes
+        to bit rows without a plane.  Targets carry `labels` and may carry `masks` (either SegmentationMask mode, or an
+        RLEMasks), `iscrowd` and `area`."""
         assert len(predictions) == len(targets), "one prediction per target"
         segm = "segm" in self.iou_types
         dev = targets[0].bbox.device if targets else torch.device("cpu")
@@ -131,9 +162,9 @@ class COCOStyleEvaluator(object):
                          for t, m in zip(tgts, has_masks)]
             if segm and not all(m or len(t) == 0 for t, m in zip(tgts, has_masks)):
                 raise ValueError("segm evaluation needs ground-truth masks")
-            gt_pack = _C.mask_pack(gt_planes)
+            gt_pack = _pack_masks(gt_planes)
         if segm:
-            dt_pack = _C.mask_pack(self._prediction_planes(preds))
+            dt_pack = _pack_masks(self._prediction_planes(preds))
         # the ground truth's area: the field; else the mask's pixel count; else w * h of the xywh box
         gt_wh = (gt_box[:, 2:] - gt_box[:, :2]) + 1
         box_area = gt_wh[:, 0].to(torch.float64) * gt_wh[:, 1].to(torch.float64)
@@ -170,7 +201,7 @@ class COCOStyleEvaluator(object):
                        gti.cpu().numpy())
 
     def _prediction_planes(self, preds):
-        """-> a list of [n_i, H_i, W_i] uint8 / bool tensors"""
+        """-> per image a [n_i, H_i, W_i] uint8 / bool tensor, or the prediction's RLEMasks as it is"""
         from maskrcnn_benchmark.modeling.roi_heads.mask_head.inference import Masker
 
         out, paste = [None] * len(preds), []
@@ -180,6 +211,11 @@ class COCOStyleEvaluator(object):
                 out[i] = torch.zeros((0, H, W), dtype=torch.uint8, device=p.bbox.device)
                 continue
             masks = p.get_field("mask")
+            if isinstance(masks, RLEMasks):
+                if tuple(masks.size) != (W, H):
+                    raise ValueError("RLE prediction masks of an image of %s for an image of %s" % (masks.size, (W, H)))
+                out[i] = masks
+                continue
             if masks.dim() != 4 or masks.shape[1] != 1:
                 raise ValueError("prediction masks must be [n, 1, H, W] planes or [n, 1, M, M] probabilities, got %s" % (tuple(masks.shape),))
             if masks.dtype == torch.bool or masks.dtype == torch.uint8:

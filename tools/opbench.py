@@ -862,6 +862,73 @@ def bench_coco_results(C, iters, copy_gbs=None):
     return out
 
 
+def bench_rle_decode(C, iters):
+    """reading result files back (csrc/rle_decode.hip, detops_mask_pack_rle of csrc/evaluate.hip): the strings of bench_coco_results' case, 100
+    detections of one 800 x 1333 image, decoded and packed into bit rows.
+    `kernels` row: the launches of the two decode calls on preallocated outputs, HIP events; bytes = the strings read by every
+    pass (5) + the runs written.  Every other row is a host clock around a device synchronise, per call:
+    _C.rle_string_decode_list from the list of str (one H2D copy, the host read of the total, the status check);
+    _C.mask_pack_rle on device runs; the numpy statements of both on the same data (host arrays in, host arrays out); and
+    the dense route to the same bit rows, _C.paste_masks + _C.mask_pack (107 MB of planes)."""
+    from maskrcnn_benchmark import _eval_cpu, _lib, _rle_cpu
+    g = torch.Generator().manual_seed(5)
+    N, H, W, M = 100, 800, 1333, 28
+    s_ = torch.exp(torch.empty(N, 2).uniform_(np.log(32), np.log(800), generator=g))
+    xy = torch.rand(N, 2, generator=g) * torch.tensor([W - 32.0, H - 32.0])
+    boxes = torch.cat([xy, xy + s_], 1).cuda()
+    maps = torch.sigmoid(3 * torch.randn(N, 1, M, M, generator=g)).cuda()
+    counts, run_offset = C.paste_masks_rle(maps, boxes, [(H, W)], 0.5, 1, counts=[N])
+    total = counts.numel()
+    data, byte_offset = C.rle_strings(counts, run_offset)
+    strings = C.rle_string_list(data, byte_offset)
+    B, hw = data.numel(), [(H, W)] * N
+    hw_d = torch.tensor(hw, dtype=torch.int32).cuda()
+    lib, ptr, st = _lib.lib, _lib.ptr, _lib.stream_of
+    nbytes = int(lib.detops_rle_decode_workspace_bytes(B, N))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
+    ro, out, status = torch.zeros_like(run_offset), torch.empty_like(counts), torch.empty((N,), dtype=torch.int32, device="cuda")
+
+    def kernels():
+        _lib.check(lib.detops_rle_decode_count(ptr(data), ptr(byte_offset), B, N, ptr(ro), ptr(ws), nbytes, st(data)), "count")
+        _lib.check(lib.detops_rle_decode_write(ptr(data), ptr(byte_offset), B, N, ptr(ro), total, ptr(hw_d), ptr(out), ptr(status),
+                                               ptr(ws), nbytes, st(data)), "write")
+
+    def wall(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e6
+
+    us = dev_time_us(kernels, iters)
+    assert torch.equal(out, counts) and torch.equal(ro, run_offset) and not bool(status.any())
+    res = [_entry("rle_decode kernels (count, offsets, sums, write, status) N=100 800x1333", us, 5 * B + total * 4,
+                  {"runs": total, "string_bytes": B})]
+    n = max(iters // 2, 10)
+    dev_us = wall(lambda: C.rle_string_decode_list(strings, hw, "cuda"), n)
+    res.append(_entry("rle_decode _C.rle_string_decode_list, list of str -> device runs (one H2D copy, two host reads)", dev_us,
+                      2 * B + total * 4))
+    np_us = wall(lambda: C.rle_string_decode_list(strings, hw), n)
+    res.append(_entry("rle_decode numpy path, list of str -> host runs", np_us, B + total * 4,
+                      {"numpy_over_device": round(np_us / dev_us, 2)}))
+    want = C.mask_pack(C.paste_masks(maps, boxes, [(H, W)], 0.5, 1, counts=[N])[1][0][:, 0])
+    got = C.mask_pack_rle(counts, run_offset, hw)
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+    words = got[0].numel() * 8
+    pack_us = wall(lambda: C.mask_pack_rle(counts, run_offset, hw), n)
+    res.append(_entry("rle_decode _C.mask_pack_rle, device runs -> bit rows (no plane)", pack_us, total * 12 + words))
+    c_h, ro_h = counts.cpu().numpy(), run_offset.cpu().numpy()
+    np_pack = wall(lambda: _eval_cpu.mask_pack_rle(c_h, ro_h, hw), 2)
+    res.append(_entry("rle_decode numpy mask_pack_rle on the same runs (host arrays)", np_pack, total * 4 + words,
+                      {"numpy_over_device": round(np_pack / pack_us, 1)}))
+    dense_us = wall(lambda: C.mask_pack(C.paste_masks(maps, boxes, [(H, W)], 0.5, 1, counts=[N])[1][0][:, 0]), n)
+    res.append(_entry("rle_decode dense route: _C.paste_masks + _C.mask_pack (planes stored)", dense_us, 2 * N * H * W + words,
+                      {"dense_over_rle": round(dense_us / pack_us, 2)}))
+    return res
+
+
 def bench_evaluation(C, iters):
     """detection evaluation (csrc/evaluate.hip): the 100 pasted detections of bench_masker against the 20 instances of
     bench_polygons, one 800 x 1333 image, all in one category (every pair is a problem pair: one problem of 100 x 20).
@@ -1014,6 +1081,8 @@ def main():
     if not only or "coco_results" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_coco_results(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
+    if not only or "rle_decode" in only:
+        res += bench_rle_decode(C, args.iters)
     if not only or "input_prep" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_input_prep(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
