@@ -826,6 +826,65 @@ int detops_eval_match(int mode, const double* iou, const int32_t* dt_offset, con
                       detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Keypoint evaluation (OKS) (csrc/eval_oks.hip; extension: the reference hands keypoints.json to pycocotools' COCOeval with
+ * iouType "keypoints").  The similarity of a detection and a ground truth is the object keypoint similarity; the matching
+ * around it is detops_eval_match, unchanged.
+ *
+ * The rules are a restatement of pycocotools.cocoeval (computeOks, the keypoint branches of _prepare, evaluateImg and
+ * setKpParams, and loadRes for keypoint results), written from knowledge of that code.  **NOBODY HAS CHECKED THIS
+ * RESTATEMENT AGAINST pycocotools**, which is not available where this project is built and tested; tests/oks_refs.py is
+ * the literal, loop-by-loop form everything here is pinned to.
+ *
+ * A problem is as above (the detections and ground truths of one (image, category) pair, sorted arrays, dt_offset /
+ * gt_offset / iou_offset), with the detections of a problem cut to 20.  Keypoints are fp32 [*, K, 3] rows of (x, y, v) as
+ * Keypoints.keypoints stores them.  For detection d and ground truth g, in fp64 with no operation contracted:
+ *     var[k] = (2 * sigma[k])^2                       sigma: fp64 [K], an INPUT
+ *     k1     = the number of k with vg[k] > 0         (the ground truth's visibility flags)
+ *     if k1 > 0:  dx[k] = xd[k] - xg[k];  dy[k] = yd[k] - yg[k]
+ *     else:       x0 = bx - bw; x1 = bx + 2*bw; y0 = by - bh; y1 = by + 2*bh
+ *                 dx[k] = max(0, x0 - xd[k]) + max(0, xd[k] - x1);  dy[k] likewise
+ *     e[k]   = (dx[k]*dx[k] + dy[k]*dy[k]) / var[k] / (area_g + 2^-52) / 2        in this order
+ *     oks    = (the sum over the k that count of exp(-e[k])) / (the number of k that count)
+ *              the k that count: those with vg[k] > 0 when k1 > 0, all K otherwise
+ *   - coordinates are widened from fp32 to fp64 before the subtraction; the detection's third column is never read;
+ *   - (bx, by, bw, bh) is BoxList.convert("xywh") of the ground truth's fp32 xyxy box, w = (x2 - x1) + 1 in fp32 (the
+ *     convention of DETOPS_EVAL_COCO_BBOX), then widened;
+ *   - area_g is the ground truth's area as the evaluator has it: the `area` field, else the mask's pixel count, else the
+ *     area of the xywh box;
+ *   - THE SUM RUNS IN KEYPOINT ORDER, ONE TERM AFTER THE OTHER, starting from 0.  pycocotools calls np.sum, which adds in
+ *     a blocked order of its own and differs from the sequential sum in the last bit for about half of random 17-term
+ *     inputs: the last bits of an OKS are THIS LIBRARY'S CHOICE and can differ from pycocotools';
+ *   - exp is the device library's fp64 exp (host path: the C library's).  Where every e[k] is 0 the result is exactly 1.
+ *   The default sigma is the COCO person table, recalled and NOT CHECKED against pycocotools:
+ *     [.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89] / 10.
+ * dt_area [D_total] fp64, the detection's area for the "unmatched detection outside the area range" rule, is
+ *   (max x - min x) * (max y - min y) over all K keypoints, the extents taken in fp32 and the two differences and the
+ *   product in fp64 (loadRes makes the result's box and area from the keypoint extents).  A NaN coordinate makes it NaN.
+ * Around it (the caller's part, data/datasets/evaluation/keypoint_oks.py):
+ *   - a ground truth is ignored in an area range when it is a crowd, when it has no visible keypoint (k1 == 0; pycocotools
+ *     reads the annotation's num_keypoints, here it is counted), or when its area lies outside the range;
+ *   - a crowd may be matched again, a ground truth with k1 == 0 may not: detops_eval_match gets gt_flag = iscrowd and, for
+ *     a ground truth with k1 == 0 that is no crowd, the area -1, which lies outside every range (the OKS above still
+ *     divides by the real area);
+ *   - area ranges all / medium / large = [[0, 1e10], [32^2, 96^2], [96^2, 1e10]], max detections (20,), the thresholds and
+ *     recall levels of the other types; the ten statistics in order: AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl.
+ *
+ * detops_eval_oks — oks [total_pairs] fp64 in the layout of detops_eval_iou and dt_area [D_total] fp64, one launch.  Every
+ *   output element is written exactly once, there are no atomics and no reduction tree: two runs give identical bits.  A
+ *   pair index outside its problem's matrix (inconsistent offsets) writes 0 and reads nothing.  THE LARGEST K SERVED IS
+ *   DETOPS_EVAL_OKS_MAX_K (a pair is half a wave, a lane per keypoint): above it the entry point returns
+ *   DETOPS_EUNSUPPORTED with nothing launched, and the caller computes the call on the host.
+ * DETOPS_EINVAL: K < 1, negative sizes, P > 0 with a null offsets array, total_pairs > 0 with P == 0 or a null dt_kpts,
+ * gt_kpts, gt_boxes, gt_area, sigmas or oks, D_total > 0 with a null dt_kpts or dt_area.
+ * total_pairs == 0 (P == 0 included) writes no oks, D_total == 0 no dt_area; both 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+#define DETOPS_EVAL_OKS_MAX_K 32
+int detops_eval_oks(const float* dt_kpts, const float* gt_kpts, const float* gt_boxes, const double* gt_area,
+                    const double* sigmas, int K, const int32_t* dt_offset, const int32_t* gt_offset,
+                    const int64_t* iou_offset, int P, int64_t D_total, int64_t total_pairs, double* oks, double* dt_area,
+                    detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Batch image preparation (csrc/image_prep.hip; extension: the reference resizes every image on the CPU with
  * torchvision over Pillow, data/transforms/transforms.py, and copies the padded fp32 batch to the device).  One launch
  * takes the raw RGB uint8 HWC images of a batch to the zero-padded fp32 batch tensor: Resize, RandomHorizontalFlip,

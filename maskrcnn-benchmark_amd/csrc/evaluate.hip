@@ -10,9 +10,9 @@
 //
 // A problem is the detections and the ground truths of one (image, category) pair.  dt_offset / gt_offset [P + 1] delimit
 // its rows and columns, iou_offset [P + 1] (int64) its D_p x G_p row-major matrix; a flat pair index finds its problem by
-// bisection of iou_offset.  The caller sizes every array from the same offsets; a pair index outside its problem's matrix
-// (inconsistent offsets) writes 0 and reads nothing.
-#include "detops_dtype.h"
+// bisection of iou_offset (eval_problem.h, shared with eval_oks.hip).  The caller sizes every array from the same offsets;
+// a pair index outside its problem's matrix (inconsistent offsets) writes 0 and reads nothing.
+#include "eval_problem.h"
 
 namespace {
 
@@ -21,23 +21,6 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kPackUnroll = 4;        // words of a plane a wave has in flight
 constexpr int kPackItems = 32;        // words per wave the grid of detops_mask_pack is sized for
 constexpr int kMaxGt = DETOPS_EVAL_MAX_GT;
-
-struct Pair {
-  int p, d, g;        // problem, detection and ground truth (indices into the sorted arrays), or p = -1
-};
-
-__device__ __forceinline__ Pair pair_of(const int32_t* __restrict__ dt_offset, const int32_t* __restrict__ gt_offset,
-                                        const int64_t* __restrict__ iou_offset, int P, int64_t idx) {
-  Pair r;
-  r.p = last_at_or_below(iou_offset, P, idx);   // the problem that owns flat pair `idx` (problems without pairs own nothing)
-  const int d0 = dt_offset[r.p], g0 = gt_offset[r.p];
-  const int D = dt_offset[r.p + 1] - d0, G = gt_offset[r.p + 1] - g0;
-  const int64_t local = idx - iou_offset[r.p];
-  if (D <= 0 || G <= 0 || local < 0 || local >= static_cast<int64_t>(D) * G) { r.p = -1; r.d = r.g = 0; return r; }
-  r.d = d0 + static_cast<int>(local / G);
-  r.g = g0 + static_cast<int>(local % G);
-  return r;
-}
 
 // ---------------------------------------------------------------------------------------------------- pack
 __global__ void mask_pack_init_kernel(const int32_t* __restrict__ plane_hw, int N, int32_t* __restrict__ area,
@@ -472,10 +455,6 @@ eval_match_voc_kernel(const double* __restrict__ iou, const int32_t* __restrict_
       match[d0 + d] = m;
     }
   }
-}
-
-bool bad_problem_args(const void* dt_offset, const void* gt_offset, const void* iou_offset, int P) {
-  return P < 0 || (P > 0 && (!dt_offset || !gt_offset || !iou_offset));
 }
 
 }  // namespace

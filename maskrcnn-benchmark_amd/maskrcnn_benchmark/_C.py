@@ -1393,6 +1393,46 @@ def eval_match(mode, iou, dt_offset, gt_offset, iou_offset, counts_host, gt_flag
     return (dtm, dti, gti) if coco else vm
 
 
+EVAL_OKS_MAX_K = _lib._abi.EVAL_OKS_MAX_K        # DETOPS_EVAL_OKS_MAX_K: the largest K detops_eval_oks serves
+
+
+def eval_oks(dt_kpts, gt_kpts, gt_boxes, gt_area, sigmas, dt_offset, gt_offset, iou_offset, total_pairs):
+    """The fp64 OKS matrices of every problem and the detections' keypoint-extent areas (extension; include/detops.h:
+    detops_eval_oks).  dt_kpts [D_total, K, 3] / gt_kpts [G_total, K, 3] fp32 rows of (x, y, v), gt_boxes fp32 xyxy
+    [G_total, 4], gt_area fp64 [G_total], everything in sorted (problem) order; sigmas fp64 [K] -> (oks float64
+    [total_pairs], dt_area float64 [D_total]).  Device tensors go to the kernel; CPU tensors, and K above EVAL_OKS_MAX_K,
+    take the numpy form of the same definition (_eval_cpu.eval_oks)."""
+    dt_offset, gt_offset, iou_offset, P = _problem_args("eval_oks", dt_offset, gt_offset, iou_offset)
+    total_pairs = int(total_pairs)
+    sigmas = torch.as_tensor(sigmas, dtype=torch.float64).reshape(-1).contiguous()
+    K = sigmas.numel()
+    if K < 1 or dt_kpts.dim() != 3 or gt_kpts.dim() != 3 or tuple(dt_kpts.shape[1:]) != (K, 3) or tuple(gt_kpts.shape[1:]) != (K, 3):
+        raise ValueError("eval_oks: expected keypoints [*, K, 3] for K = %d sigmas, got %s and %s"
+                         % (K, tuple(dt_kpts.shape), tuple(gt_kpts.shape)))
+    dt_kpts, gt_kpts = dt_kpts.to(torch.float32).contiguous(), gt_kpts.to(torch.float32).contiguous()
+    gt_boxes = gt_boxes.to(torch.float32).contiguous().reshape(-1, 4)
+    gt_area = gt_area.to(torch.float64).contiguous().reshape(-1)
+    D_total, G_total = dt_kpts.shape[0], gt_kpts.shape[0]
+    if gt_boxes.shape[0] != G_total or gt_area.numel() != G_total:
+        raise ValueError("eval_oks: gt_boxes and gt_area do not match the %d ground truths" % G_total)
+    tensors = (dt_kpts, gt_kpts, gt_boxes, gt_area, dt_offset, gt_offset, iou_offset)
+    dev = dt_offset.device
+    if not any(on_device(t) for t in tensors) or K > EVAL_OKS_MAX_K:
+        oks, area = _eval_cpu.eval_oks(_np(dt_kpts), _np(gt_kpts), _np(gt_boxes), _np(gt_area), sigmas.cpu().numpy(),
+                                       _np(dt_offset), _np(gt_offset), _np(iou_offset))
+        return torch.from_numpy(oks).to(dev), torch.from_numpy(area).to(dev)
+    _need_cuda("eval_oks", *tensors)
+    sigmas = sigmas.to(dev)
+    oks = torch.empty((total_pairs,), dtype=torch.float64, device=dev)
+    area = torch.empty((D_total,), dtype=torch.float64, device=dev)
+    if total_pairs or D_total:
+        with _on_device(oks), _timed(("eval_oks[pairs=%d,K=%d]", (total_pairs, K)), oks):
+            check(lib.detops_eval_oks(ptr(dt_kpts), ptr(gt_kpts), ptr(gt_boxes), ptr(gt_area), ptr(sigmas), K, ptr(dt_offset),
+                                      ptr(gt_offset), ptr(iou_offset), P, D_total, total_pairs, ptr(oks), ptr(area),
+                                      stream_of(oks)), "eval_oks")
+    return oks, area
+
+
 def match_labels(matched, gt_labels=None, valid=None, dtype=torch.int64):
     """Matcher output [N,K] -> labels in one launch (extension; reference modeling/rpn/loss.py:70-88,
     roi_heads/box_head/loss.py:56-72): matched >= 0 -> gt_labels[n, matched] (1 when gt_labels is None), -1 -> 0,

@@ -216,3 +216,52 @@ def eval_match(mode, iou, dt_offset, gt_offset, iou_offset, dt_area, gt_area, gt
                                           gt_flag[g0:g1], iou_thrs, area_rngs)
             dtm[:, :, d0:d1], dti[:, :, d0:d1], gti[:, g0:g1] = a, b, c
     return out if mode == VOC else (dtm, dti, gti)
+
+
+# ------------------------------------------------------------------------------------------------ keypoints (OKS)
+OKS_MAX_K = 32   # DETOPS_EVAL_OKS_MAX_K
+# the COCO person table (pycocotools' kpt_oks_sigmas), recalled and not checked against it
+COCO_PERSON_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+
+
+def eval_oks(dt_kpts, gt_kpts, gt_boxes, gt_area, sigmas, dt_offset, gt_offset, iou_offset):
+    """include/detops.h, "Keypoint evaluation (OKS)": keypoints fp32 [D_total, K, 3] / [G_total, K, 3], gt_boxes fp32 xyxy,
+    gt_area and sigmas fp64, everything in sorted (problem) order -> (oks float64 [total_pairs], dt_area float64 [D_total]).
+    Vectorised over the pairs; the sum over the keypoints is a loop, one term after the other, as the definition has it."""
+    sig = np.asarray(sigmas, np.float64).reshape(-1)
+    K = sig.size
+    dk = np.asarray(dt_kpts, np.float32).reshape(-1, K, 3)
+    gk = np.asarray(gt_kpts, np.float32).reshape(-1, K, 3)
+    x, y = dk[:, :, 0], dk[:, :, 1]
+    if dk.shape[0]:
+        dt_area = (x.max(axis=1).astype(np.float64) - x.min(axis=1).astype(np.float64)) \
+            * (y.max(axis=1).astype(np.float64) - y.min(axis=1).astype(np.float64))
+    else:
+        dt_area = np.zeros((0,), np.float64)
+    d, g = _pairs(dt_offset, gt_offset, iou_offset)
+    if d.size == 0:
+        return np.zeros((0,), np.float64), dt_area
+    xd, yd = x[d].astype(np.float64), y[d].astype(np.float64)
+    xg, yg = gk[g, :, 0].astype(np.float64), gk[g, :, 1].astype(np.float64)
+    visible = gk[g, :, 2] > 0
+    k1 = visible.sum(axis=1)
+    has = (k1 > 0)[:, None]
+    one = np.float32(1)
+    gb = np.asarray(gt_boxes, np.float32).reshape(-1, 4)[g]
+    bw = ((gb[:, 2] - gb[:, 0]) + one).astype(np.float64)[:, None]        # BoxList.convert("xywh"), fp32
+    bh = ((gb[:, 3] - gb[:, 1]) + one).astype(np.float64)[:, None]
+    bx, by = gb[:, 0].astype(np.float64)[:, None], gb[:, 1].astype(np.float64)[:, None]
+    x0, x1, y0, y1 = bx - bw, bx + 2.0 * bw, by - bh, by + 2.0 * bh
+    dx = np.where(has, xd - xg, np.fmax(0.0, x0 - xd) + np.fmax(0.0, xd - x1))
+    dy = np.where(has, yd - yg, np.fmax(0.0, y0 - yd) + np.fmax(0.0, yd - y1))
+    s2 = 2.0 * sig
+    var = s2 * s2
+    area = np.asarray(gt_area, np.float64).reshape(-1)[g] + np.spacing(1)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        e = (dx * dx + dy * dy) / var[None, :] / area[:, None] / 2.0
+        term = np.exp(-e)
+    counts = np.where(has, visible, True)
+    s = np.zeros((d.size,), np.float64)
+    for k in range(K):
+        s = np.where(counts[:, k], s + term[:, k], s)
+    return s / np.where(k1 > 0, k1, K).astype(np.float64), dt_area

@@ -1,8 +1,12 @@
 """Detection evaluation (reference data/datasets/evaluation/): `evaluate` dispatches on the dataset as the reference's
 does; COCO-shaped datasets go to the streaming COCO-style evaluator (coco_style.py), VOC-shaped ones to voc.py.
 
-Not built, and raising NotImplementedError: `box_only` (the AR of RPN proposals), the `keypoints` IoU type (OKS) and the
-Cityscapes evaluator.
+Keypoints are scored under names of their own (keypoint_oks.py: KeypointOKSEvaluator, load_keypoint_results,
+evaluate_keypoint_file; `inference(keypoint_oks=True)`; tools/evaluate_keypoints.py).  `evaluate`, `check_scope` and
+COCOStyleEvaluator still refuse the `keypoints` IoU type: routing the generic names to OKS is a later change.
+
+Not built, and raising NotImplementedError: `box_only` (the AR of RPN proposals), the `keypoints` IoU type through the
+generic entry points and the Cityscapes evaluator.
 """
 import logging
 import os
@@ -11,6 +15,8 @@ from collections import OrderedDict
 import torch
 
 from .coco_style import COCOStyleEvaluator, STAT_NAMES
+from .keypoint_oks import KeypointOKSEvaluator, evaluate_keypoint_file, load_keypoint_results  # noqa: F401
+from .keypoint_oks import STAT_NAMES as KEYPOINT_STAT_NAMES
 from .voc import do_voc_evaluation, eval_detection_voc  # noqa: F401
 
 
@@ -42,7 +48,8 @@ def check_scope(box_only, iou_types):
     if box_only:
         raise NotImplementedError("box_only (the AR of RPN proposals) is not built")
     if "keypoints" in iou_types:
-        raise NotImplementedError("the keypoints IoU type (OKS) is not built")
+        raise NotImplementedError("the keypoints IoU type is not served by the generic entry points: OKS runs through "
+                                  "inference(keypoint_oks=True), KeypointOKSEvaluator and tools/evaluate_keypoints.py")
 
 
 def _groundtruth(dataset, index):
@@ -62,27 +69,32 @@ def coco_evaluation(dataset, predictions, output_folder, box_only=False, iou_typ
 
 
 def finish_coco(evaluator, output_folder=None, expected_results=(), expected_results_sigma_tol=4):
-    """summarize, log the table, check the expected results, save coco_results.pth -> COCOResults"""
+    """summarize, log the table, check the expected results, save coco_results.pth -> COCOResults.  evaluator: a
+    COCOStyleEvaluator, a KeypointOKSEvaluator, or a sequence of them (their tables in that order)"""
     logger = logging.getLogger("maskrcnn_benchmark.inference")
-    evaluator.summarize()
-    results = COCOResults(*evaluator.iou_types)
-    results.update(evaluator)
+    evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [evaluator]
+    stats = OrderedDict()
+    for e in evaluators:
+        stats.update(e.summarize())
+    results = COCOResults(*stats)
+    for e in evaluators:
+        results.update(e)
     logger.info(results)
-    logger.info(format_stats(evaluator.stats))
+    logger.info(format_stats(stats))
     check_expected_results(results, expected_results, expected_results_sigma_tol)
     if output_folder:
         torch.save(results, os.path.join(output_folder, "coco_results.pth"))
         with open(os.path.join(output_folder, "coco_results.txt"), "w") as f:
-            f.write(repr(results) + format_stats(evaluator.stats))
+            f.write(repr(results) + format_stats(stats))
     return results
 
 
 def format_stats(stats):
-    """{iou type: the 12 numbers} -> the table as text"""
+    """{iou type: the 12 numbers (keypoints: the 10 of keypoint_oks.STAT_NAMES)} -> the table as text"""
     text = "\n"
     for iou_type, s in stats.items():
         text += "%s\n" % iou_type
-        text += "".join("  %-6s %8.4f\n" % (n, v) for n, v in zip(STAT_NAMES, s))
+        text += "".join("  %-6s %8.4f\n" % (n, v) for n, v in zip(KEYPOINT_STAT_NAMES if iou_type == "keypoints" else STAT_NAMES, s))
     return text
 
 
@@ -116,7 +128,8 @@ class COCOResults(object):
             self.results[task] = OrderedDict.fromkeys(self.METRICS[task], -1)
 
     def update(self, evaluator):
-        """evaluator: a summarized COCOStyleEvaluator (the reference takes a pycocotools COCOeval), or None"""
+        """evaluator: a summarized COCOStyleEvaluator or KeypointOKSEvaluator (the reference takes a pycocotools COCOeval),
+        or None.  The keypoints row takes the first five of the ten keypoint statistics: AP, AP50, AP75, APm, APl."""
         if evaluator is None:
             return
         assert isinstance(evaluator, COCOStyleEvaluator)

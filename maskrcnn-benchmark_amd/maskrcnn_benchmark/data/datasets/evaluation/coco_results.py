@@ -19,7 +19,11 @@ Reading them back: `load_results` turns `bbox.json` / `segm.json` (this project'
 evaluator takes, the masks as RLEMasks decoded by `_C.rle_string_decode_list` (include/detops.h, "Reading compressed RLE
 strings"); `evaluate_result_files` scores the files against a dataset's ground truth (tools/evaluate_results.py).
 
-Not built: `box_only` proposals, OKS (so `keypoints.json` is written but cannot be scored)."""
+`keypoints.json` is read back and scored under names of their own, keypoint_oks.load_keypoint_results and
+keypoint_oks.evaluate_keypoint_file (tools/evaluate_keypoints.py); `load_results` and `evaluate_result_files` still refuse
+"keypoints".
+
+Not built: `box_only` proposals."""
 import json
 import os
 
@@ -195,7 +199,7 @@ def load_results(path_or_list, dataset, iou_type, device=None):
     becomes the `mask` field, an RLEMasks on `device` (every string of the file in ONE _C.rle_string_decode_list call).
     ValueError: an unknown image id or category id, a polygon, an RLE of another size than its image, malformed strings."""
     if iou_type == "keypoints":
-        raise NotImplementedError("reading keypoints.json for scoring (OKS) is not built")
+        raise NotImplementedError("keypoints.json is read by keypoint_oks.load_keypoint_results, not by load_results")
     if iou_type not in ("bbox", "segm"):
         raise ValueError("load_results: unknown iou type %r" % (iou_type,))
     entries = _read_entries(path_or_list)
@@ -252,11 +256,12 @@ def evaluate_result_files(dataset, files, output_folder=None, batch=8, device="c
     list of entries serves as a path).  One COCOStyleEvaluator per file, fed `batch` images at a time on `device`; the
     masks of segm.json go from runs to bit rows there (_C.mask_pack_rle), no plane is laid out.  -> the COCOResults of
     finish_coco, which also logs the tables and, with `output_folder`, writes coco_results.pth / coco_results.txt.
-    `keypoints` raises NotImplementedError: OKS is not built."""
+    `keypoints` raises NotImplementedError: keypoints.json is scored by keypoint_oks.evaluate_keypoint_file."""
     from . import COCOStyleEvaluator, _groundtruth, finish_coco
 
     if "keypoints" in files:
-        raise NotImplementedError("the keypoints IoU type (OKS) is not built: keypoints.json cannot be scored")
+        raise NotImplementedError("keypoints.json is scored by keypoint_oks.evaluate_keypoint_file (tools/evaluate_keypoints.py), "
+                                  "not by evaluate_result_files")
     iou_types = tuple(t for t in ("bbox", "segm") if t in files)
     unknown = sorted(set(files) - set(iou_types))
     if unknown or not iou_types:

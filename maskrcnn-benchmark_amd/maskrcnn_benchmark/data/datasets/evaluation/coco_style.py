@@ -97,6 +97,35 @@ def _planes_of_target(target):
     return (masks != 0) if masks.dtype not in (torch.uint8, torch.bool) else masks
 
 
+def groundtruth_planes(tgts, dev):
+    """per target its mask planes (_planes_of_target), all-zero planes for a target without masks"""
+    return [_planes_of_target(t) if t.has_field("masks") else torch.zeros((len(t), t.size[1], t.size[0]), dtype=torch.uint8, device=dev)
+            for t in tgts]
+
+
+def groundtruth_area(tgts, gt_box, gt_pack):
+    """The ground truths' areas, fp64 [G]: the `area` field; else the mask's pixel count (gt_pack: _pack_masks of
+    groundtruth_planes, needed only then); else w * h of the xywh box.  gt_box: the targets' xyxy boxes, concatenated."""
+    dev = gt_box.device
+    gt_wh = (gt_box[:, 2:] - gt_box[:, :2]) + 1
+    box_area = gt_wh[:, 0].to(torch.float64) * gt_wh[:, 1].to(torch.float64)
+    parts, k = [], 0
+    for t in tgts:
+        n = len(t)
+        if t.has_field("area"):
+            parts.append(t.get_field("area").to(device=dev, dtype=torch.float64).reshape(-1))
+        elif t.has_field("masks"):
+            parts.append(gt_pack[3][k:k + n].to(torch.float64))
+        else:
+            parts.append(box_area[k:k + n])
+        k += n
+    return torch.cat(parts) if parts else torch.zeros((0,), dtype=torch.float64, device=dev)
+
+
+def needs_mask_area(tgts):
+    return any(t.has_field("masks") and not t.has_field("area") for t in tgts)
+
+
 class COCOStyleEvaluator(object):
     """evaluator = COCOStyleEvaluator(("bbox", "segm"), num_classes); evaluator.update(predictions, targets) per batch;
     evaluator.summarize() -> {iou type: the 12 numbers AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl}.
@@ -108,7 +137,7 @@ class COCOStyleEvaluator(object):
         iou_types = tuple(iou_types)
         for t in iou_types:
             if t == "keypoints":
-                raise NotImplementedError("the keypoints IoU type (OKS) is not built")
+                raise NotImplementedError("the keypoints IoU type is scored by keypoint_oks.KeypointOKSEvaluator, not by this class")
             if t not in ("bbox", "segm"):
                 raise ValueError("unknown IoU type %r" % (t,))
         self.iou_types = iou_types
@@ -157,28 +186,14 @@ class COCOStyleEvaluator(object):
         do, go = pr["dt_order"], pr["gt_order"]
         has_masks = [t.has_field("masks") for t in tgts]
         gt_pack = dt_pack = None
-        if segm or any(m and not t.has_field("area") for t, m in zip(tgts, has_masks)):    # planes, or their pixel counts
-            gt_planes = [_planes_of_target(t) if m else torch.zeros((len(t), t.size[1], t.size[0]), dtype=torch.uint8, device=dev)
-                         for t, m in zip(tgts, has_masks)]
+        if segm or needs_mask_area(tgts):    # planes, or their pixel counts
+            gt_planes = groundtruth_planes(tgts, dev)
             if segm and not all(m or len(t) == 0 for t, m in zip(tgts, has_masks)):
                 raise ValueError("segm evaluation needs ground-truth masks")
             gt_pack = _pack_masks(gt_planes)
         if segm:
             dt_pack = _pack_masks(self._prediction_planes(preds))
-        # the ground truth's area: the field; else the mask's pixel count; else w * h of the xywh box
-        gt_wh = (gt_box[:, 2:] - gt_box[:, :2]) + 1
-        box_area = gt_wh[:, 0].to(torch.float64) * gt_wh[:, 1].to(torch.float64)
-        parts, k = [], 0
-        for t, m in zip(tgts, has_masks):
-            n = len(t)
-            if t.has_field("area"):
-                parts.append(t.get_field("area").to(device=dev, dtype=torch.float64).reshape(-1))
-            elif m:
-                parts.append(gt_pack[3][k:k + n].to(torch.float64))
-            else:
-                parts.append(box_area[k:k + n])
-            k += n
-        gt_area = cat(parts, dtype=torch.float64, device=dev)
+        gt_area = groundtruth_area(tgts, gt_box, gt_pack)
         offs = (pr["dt_offset"], pr["gt_offset"], pr["iou_offset"])
         thrs, rngs = torch.from_numpy(self.iou_thrs), torch.from_numpy(self.area_rngs)
         for iou_type in self.iou_types:

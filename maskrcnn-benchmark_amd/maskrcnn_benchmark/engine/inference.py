@@ -2,7 +2,8 @@
 model(images.to(device)) -> targets to the device -> evaluator.update; the predictions are matched against the ground truth
 where they were made and only the match records are kept (data/datasets/evaluation/coco_style.py).  With an output folder the
 detections themselves are written as COCO result files (data/datasets/evaluation/coco_results.py: bbox.json, segm.json,
-keypoints.json), batch by batch next to the evaluator; `evaluate=False` writes them and matches nothing.  Single process only.
+keypoints.json), batch by batch next to the evaluator; `evaluate=False` writes them and matches nothing.  Keypoints are
+scored on request (`keypoint_oks=True`: data/datasets/evaluation/keypoint_oks.py).  Single process only.
 Datasets that are not COCO-shaped keep the reference's flow: the predictions are collected and handed to `evaluate`."""
 import logging
 import os
@@ -13,6 +14,7 @@ import torch
 from maskrcnn_benchmark.data.datasets.evaluation import COCOStyleEvaluator, check_scope, dataset_style, finish_coco
 from maskrcnn_benchmark.data.datasets.evaluation import evaluate as evaluate_predictions
 from maskrcnn_benchmark.data.datasets.evaluation.coco_results import COCOResultsWriter
+from maskrcnn_benchmark.data.datasets.evaluation.keypoint_oks import KeypointOKSEvaluator
 from maskrcnn_benchmark.utils.comm import get_world_size
 
 
@@ -30,7 +32,8 @@ def _built_with(model):
 
 
 def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, bbox_aug=None, device="cuda",
-              expected_results=(), expected_results_sigma_tol=4, output_folder=None, cfg=None, evaluate=True):
+              expected_results=(), expected_results_sigma_tol=4, output_folder=None, cfg=None, evaluate=True,
+              keypoint_oks=False):
     """bbox_aug: test-time box augmentation (engine/bbox_aug.py) with the passes of `cfg.TEST.BBOX_AUG`; model and loader
     were built from that `cfg` (the reference reads its global cfg there; left out, it is the copy the ROI heads keep).
     None, the default and what tools/test_net.py gets: as the model was built, i.e. TEST.BBOX_AUG.ENABLED of its config.
@@ -39,8 +42,11 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     which is logged.
     evaluate=False (COCO-shaped datasets, `output_folder` required): results only.  The model runs and the result files of
     `iou_types` are written; no evaluator is built, the evaluator's scope is not checked ("keypoints" is allowed: OKS is not
-    needed to write keypoints.json) and the targets are neither moved nor matched: the way to run a keypoint model or a test
-    set without annotations.  -> {iou type: path of its file}."""
+    needed to write keypoints.json) and the targets are neither moved nor matched: the way to run a test set without
+    annotations.  -> {iou type: path of its file}.
+    keypoint_oks=True (COCO-shaped datasets, a model with a keypoint head, not under box augmentation): the loop also feeds a
+    KeypointOKSEvaluator next to the evaluator of `iou_types`, the writer also writes keypoints.json, and the returned
+    COCOResults has a `keypoints` row.  "keypoints" in `iou_types` is still refused: OKS has names of its own."""
     if not evaluate and not output_folder:
         raise ValueError("inference(evaluate=False) writes result files only: it needs output_folder=")
     if get_world_size() > 1:
@@ -70,15 +76,20 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     dataset = data_loader.dataset
     logger.info("Start evaluation on {} dataset({} images).".format(dataset_name, len(dataset)))
     streaming = dataset_style(dataset) == "coco"
-    evaluator = writer = None
+    evaluator = writer = kp_evaluator = None
+    if keypoint_oks and (not streaming or box_only or bbox_aug):
+        raise NotImplementedError("inference(keypoint_oks=True): keypoints are scored for COCO-shaped datasets and detections "
+                                  "only (not box_only proposals, not under box augmentation)")
     if not evaluate and (not streaming or box_only):
         raise NotImplementedError("inference(evaluate=False): result files are written for COCO-shaped datasets and detections "
                                   "only (not box_only proposals)")
     if streaming and evaluate:
         check_scope(box_only, iou_types)
         evaluator = COCOStyleEvaluator(iou_types, getattr(dataset, "num_classes", None) or 81)
+        if keypoint_oks:
+            kp_evaluator = KeypointOKSEvaluator(getattr(dataset, "num_classes", None) or 2)
     if streaming and output_folder and not box_only:
-        writer = COCOResultsWriter(dataset, iou_types)
+        writer = COCOResultsWriter(dataset, tuple(iou_types) + (("keypoints",) if keypoint_oks and "keypoints" not in iou_types else ()))
     model.eval()
     predictions = {}
     start = time.time()
@@ -97,7 +108,10 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
             if writer is not None:
                 writer.update(output, image_ids)
             if evaluator is not None:
-                evaluator.update(output, [t.to(device) for t in targets])
+                targets = [t.to(device) for t in targets]
+                evaluator.update(output, targets)
+                if kp_evaluator is not None:
+                    kp_evaluator.update(output, targets)
             elif not streaming:
                 predictions.update({i: o.to("cpu") for i, o in zip(image_ids, output)})
     total = time.time() - start
@@ -116,7 +130,8 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     if streaming:
         logger.info("Matched {} detections against {} ground truths of {} images".format(
             evaluator.num_detections, evaluator.num_groundtruths, evaluator.num_images))
-        return finish_coco(evaluator, output_folder, expected_results, expected_results_sigma_tol)
+        return finish_coco(evaluator if kp_evaluator is None else [evaluator, kp_evaluator], output_folder, expected_results,
+                           expected_results_sigma_tol)
     predictions = [predictions[i] for i in sorted(predictions)]
     if output_folder:
         torch.save(predictions, os.path.join(output_folder, "predictions.pth"))

@@ -1013,6 +1013,66 @@ def bench_evaluation(C, iters):
     return out
 
 
+def bench_keypoint_oks(C, iters):
+    """keypoint evaluation (csrc/eval_oks.hip): a batch of 8 images, one category, 20 detections by 8 ground truths each,
+    K = 17 (1280 pairs, 21760 terms).  Rows: the entry point alone on prebuilt device arrays; _C.eval_oks through the
+    wrapper (its contiguity / dtype checks, the sigma copy and two allocations included); a broadcast torch formulation of
+    the same definition on the same device tensors (torch.sum adds in a tree: the last bits differ).  bytes = the keypoints,
+    boxes and areas read once + the matrix and the areas written."""
+    from maskrcnn_benchmark import _eval_cpu, _lib
+    I, D, G, K = 8, 20, 8, 17
+    rng = np.random.RandomState(3)
+    gk = np.concatenate([rng.uniform(0, 600, (I * G, K, 2)), rng.randint(0, 3, (I * G, K, 1))], axis=2).astype(np.float32)
+    gk[::7, :, 2] = 0                                         # some ground truths without a visible keypoint
+    lo, hi = gk[:, :, :2].min(axis=1), gk[:, :, :2].max(axis=1)
+    gb = np.concatenate([lo, hi], axis=1).astype(np.float32)
+    ga = ((hi - lo).prod(axis=1) * 0.6).astype(np.float64)
+    dk = np.repeat(gk.reshape(I, G, K, 3), 3, axis=1)[:, :D].reshape(I * D, K, 3).copy()
+    dk[:, :, :2] += rng.normal(0, 12, (I * D, K, 2)).astype(np.float32)
+    sig = _eval_cpu.COCO_PERSON_SIGMAS
+    dto, gto = np.arange(I + 1, dtype=np.int32) * D, np.arange(I + 1, dtype=np.int32) * G
+    ioo = np.arange(I + 1, dtype=np.int64) * (D * G)
+    dk_d, gk_d, gb_d, ga_d, sig_d, dto_d, gto_d, ioo_d = (_t(a) for a in (dk, gk, gb, ga, sig, dto, gto, ioo))
+    total = I * D * G
+    alg = (dk.size + gk.size + gb.size) * 4 + ga.size * 8 + total * 8 + I * D * 8
+    oks = torch.empty((total,), dtype=torch.float64, device="cuda")
+    area = torch.empty((I * D,), dtype=torch.float64, device="cuda")
+    raw = lambda: _lib.check(_lib.lib.detops_eval_oks(  # noqa: E731
+        dk_d.data_ptr(), gk_d.data_ptr(), gb_d.data_ptr(), ga_d.data_ptr(), sig_d.data_ptr(), K, dto_d.data_ptr(), gto_d.data_ptr(),
+        ioo_d.data_ptr(), I, I * D, total, oks.data_ptr(), area.data_ptr(), _lib.stream_of(oks)), "eval_oks")
+    out = [_entry("detops_eval_oks entry point, 8 x (20 x 8) pairs, K=17", dev_time_us(raw, iters), alg)]
+    wrapped = lambda: C.eval_oks(dk_d, gk_d, gb_d, ga_d, sig, dto_d, gto_d, ioo_d, total)  # noqa: E731
+    out.append(_entry("_C.eval_oks through the wrapper, same batch", dev_time_us(wrapped, iters), alg))
+    ref, ref_area = _eval_cpu.eval_oks(dk, gk, gb, ga, sig, dto, gto, ioo)
+    got, got_area = wrapped()
+    out[-1].update({"max_abs_diff_vs_numpy": float(np.abs(got.cpu().numpy() - ref).max()),
+                    "areas_equal": bool(np.array_equal(got_area.cpu().numpy(), ref_area))})
+    var = (2.0 * sig_d) * (2.0 * sig_d)
+
+    def torch_oks():
+        d, g = dk_d.view(I, D, 1, K, 3).double(), gk_d.view(I, 1, G, K, 3).double()
+        vis = g[..., 2] > 0
+        has = vis.any(dim=-1, keepdim=True)
+        wh = ((gb_d[:, 2:] - gb_d[:, :2]) + 1).double().view(I, 1, G, 1, 2)
+        xy = gb_d[:, :2].double().view(I, 1, G, 1, 2)
+        p = d[..., :2]
+        far = torch.clamp((xy - wh) - p, min=0) + torch.clamp(p - (xy + 2.0 * wh), min=0)
+        delta = torch.where(has.unsqueeze(-1), p - g[..., :2], far)
+        e = (delta[..., 0] * delta[..., 0] + delta[..., 1] * delta[..., 1]) / var / (ga_d.view(I, 1, G, 1) + 2.0 ** -52) / 2
+        counts = vis | ~has
+        s = torch.where(counts, torch.exp(-e), torch.zeros_like(e)).sum(dim=-1)
+        xs, ys = dk_d[:, :, 0], dk_d[:, :, 1]
+        a = (xs.max(dim=1)[0].double() - xs.min(dim=1)[0].double()) * (ys.max(dim=1)[0].double() - ys.min(dim=1)[0].double())
+        return (s / counts.sum(dim=-1)).reshape(-1), a
+
+    us = dev_time_us(torch_oks, iters)
+    t_oks, t_area = torch_oks()
+    out.append(_entry("torch: broadcast formulation on the same device tensors", us, alg,
+                      {"max_abs_diff_vs_numpy": float(np.abs(t_oks.cpu().numpy() - ref).max()),
+                       "areas_equal": bool(np.array_equal(t_area.cpu().numpy(), ref_area))}))
+    return out
+
+
 def copy_ceiling(iters):
     a = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
     b = torch.empty_like(a)
@@ -1078,6 +1138,8 @@ def main():
         res += bench_polygons(C, args.iters)
     if not only or "evaluation" in only:
         res += bench_evaluation(C, args.iters)
+    if not only or "keypoint_oks" in only:
+        res += bench_keypoint_oks(C, args.iters)
     if not only or "coco_results" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_coco_results(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
