@@ -14,9 +14,8 @@ from collections import OrderedDict
 
 import torch
 
-from .coco_style import COCOStyleEvaluator, STAT_NAMES
+from .coco_style import STAT_NAMES, STAT_ROWS, COCOStyleEvaluator, _feed, _num_classes  # noqa: F401
 from .keypoint_oks import KeypointOKSEvaluator, evaluate_keypoint_file, load_keypoint_results  # noqa: F401
-from .keypoint_oks import STAT_NAMES as KEYPOINT_STAT_NAMES
 from .voc import do_voc_evaluation, eval_detection_voc  # noqa: F401
 
 
@@ -52,19 +51,10 @@ def check_scope(box_only, iou_types):
                                   "inference(keypoint_oks=True), KeypointOKSEvaluator and tools/evaluate_keypoints.py")
 
 
-def _groundtruth(dataset, index):
-    return dataset.get_groundtruth(index) if hasattr(dataset, "get_groundtruth") else dataset[index][1]
-
-
 def coco_evaluation(dataset, predictions, output_folder, box_only=False, iou_types=("bbox",), expected_results=(),
                     expected_results_sigma_tol=4, batch=8):
     check_scope(box_only, iou_types)
-    num_classes = getattr(dataset, "num_classes", None) or 81
-    evaluator = COCOStyleEvaluator(iou_types, num_classes)
-    for i in range(0, len(predictions), batch):
-        preds = list(predictions[i:i + batch])
-        dev = preds[0].bbox.device
-        evaluator.update(preds, [_groundtruth(dataset, j).to(dev) for j in range(i, i + len(preds))])
+    evaluator = _feed(COCOStyleEvaluator(iou_types, _num_classes(dataset, 81)), predictions, dataset, batch)
     return finish_coco(evaluator, output_folder, expected_results, expected_results_sigma_tol)
 
 
@@ -90,11 +80,11 @@ def finish_coco(evaluator, output_folder=None, expected_results=(), expected_res
 
 
 def format_stats(stats):
-    """{iou type: the 12 numbers (keypoints: the 10 of keypoint_oks.STAT_NAMES)} -> the table as text"""
+    """{iou type: its statistics, in the order of coco_style.STAT_ROWS (12 numbers; keypoints: 10)} -> the table as text"""
     text = "\n"
     for iou_type, s in stats.items():
         text += "%s\n" % iou_type
-        text += "".join("  %-6s %8.4f\n" % (n, v) for n, v in zip(KEYPOINT_STAT_NAMES if iou_type == "keypoints" else STAT_NAMES, s))
+        text += "".join("  %-6s %8.4f\n" % (row[0], v) for row, v in zip(STAT_ROWS[iou_type], s))
     return text
 
 

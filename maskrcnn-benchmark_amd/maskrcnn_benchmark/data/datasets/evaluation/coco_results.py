@@ -35,6 +35,8 @@ from maskrcnn_benchmark.modeling.roi_heads.mask_head.inference import paste_mask
 from maskrcnn_benchmark.structures.bounding_box import BoxList
 from maskrcnn_benchmark.structures.rle_masks import RLEMasks
 
+from .coco_style import COCOStyleEvaluator, _feed, _num_classes
+
 IOU_TYPES = ("bbox", "segm", "keypoints")
 MASK_THRESHOLD, MASK_PADDING = 0.5, 1      # the reference's Masker(threshold=0.5, padding=1)
 
@@ -169,6 +171,38 @@ def _read_entries(path_or_list):
     return path_or_list
 
 
+def _group_entries(path_or_list, dataset):
+    """-> (the file's entries, per image of the dataset its entries in file order, the map from category id to label or
+    None): entries go to their image through the inverse of `id_to_img_map`, labels come through
+    `json_category_id_to_contiguous_id`; a dataset without these maps uses the index and the label, as the writer does.
+    ValueError: an image id or a category id the dataset does not have."""
+    entries = _read_entries(path_or_list)
+    ids = getattr(dataset, "id_to_img_map", None)
+    index_of = {v: k for k, v in ids.items()} if ids is not None else None
+    labels_of = getattr(dataset, "json_category_id_to_contiguous_id", None)
+    if labels_of is None and getattr(dataset, "contiguous_category_id_to_json_id", None) is not None:
+        labels_of = {v: k for k, v in dataset.contiguous_category_id_to_json_id.items()}
+    per_image = [[] for _ in range(len(dataset))]
+    for e in entries:
+        image_id = e["image_id"]
+        index = index_of.get(image_id) if index_of is not None else (image_id if isinstance(image_id, int) else None)
+        if index is None or not 0 <= index < len(per_image):
+            raise ValueError("result files: image_id %r is not in the dataset" % (image_id,))
+        if labels_of is not None and e["category_id"] not in labels_of:
+            raise ValueError("result files: category_id %r is not in the dataset" % (e["category_id"],))
+        per_image[index].append(e)
+    return entries, per_image, labels_of
+
+
+def _scored_boxlist(boxes, size, mode, es, labels_of):
+    """the xyxy BoxList of an image's entries `es`, with their `scores` and `labels`; boxes: theirs, [len(es), 4] in `mode`"""
+    boxlist = BoxList(boxes, size, mode=mode).convert("xyxy")
+    boxlist.add_field("scores", torch.tensor([e["score"] for e in es], dtype=torch.float32))
+    cats = [e["category_id"] for e in es]
+    boxlist.add_field("labels", torch.tensor(cats if labels_of is None else [labels_of[c] for c in cats], dtype=torch.int64))
+    return boxlist
+
+
 def _segmentation_string(entry, height, width):
     """the entry's `segmentation` as a compressed string; an uncompressed counts list is coded by the numpy coder, so that
     one decode call checks and unpacks every mask of the file alike"""
@@ -191,10 +225,9 @@ def _segmentation_string(entry, height, width):
 
 def load_results(path_or_list, dataset, iou_type, device=None):
     """A `bbox.json` / `segm.json` result file (a path, or its list of entries) -> a list of BoxList in dataset order, what
-    COCOStyleEvaluator.update takes: the inverse of the writer.  Entries are grouped by `image_id` through the inverse of
-    `id_to_img_map` and keep the file's order inside an image (the evaluator's stable sort then reproduces ties); labels
-    come through `json_category_id_to_contiguous_id`; a dataset without these maps uses the index and the label, as the
-    writer does.  `bbox` goes from xywh through BoxList(mode="xywh").convert("xyxy"); a segm entry without `bbox` gets the
+    COCOStyleEvaluator.update takes: the inverse of the writer.  Entries are grouped by image and labelled as
+    _group_entries does, and keep the file's order inside an image (the evaluator's stable sort then reproduces ties).
+    `bbox` goes from xywh through BoxList(mode="xywh").convert("xyxy"); a segm entry without `bbox` gets the
     full-image box, which the segm rules never read.  `segmentation` is a compressed string or an uncompressed list and
     becomes the `mask` field, an RLEMasks on `device` (every string of the file in ONE _C.rle_string_decode_list call).
     ValueError: an unknown image id or category id, a polygon, an RLE of another size than its image, malformed strings."""
@@ -202,21 +235,7 @@ def load_results(path_or_list, dataset, iou_type, device=None):
         raise NotImplementedError("keypoints.json is read by keypoint_oks.load_keypoint_results, not by load_results")
     if iou_type not in ("bbox", "segm"):
         raise ValueError("load_results: unknown iou type %r" % (iou_type,))
-    entries = _read_entries(path_or_list)
-    ids = getattr(dataset, "id_to_img_map", None)
-    index_of = {v: k for k, v in ids.items()} if ids is not None else None
-    labels_of = getattr(dataset, "json_category_id_to_contiguous_id", None)
-    if labels_of is None and getattr(dataset, "contiguous_category_id_to_json_id", None) is not None:
-        labels_of = {v: k for k, v in dataset.contiguous_category_id_to_json_id.items()}
-    per_image = [[] for _ in range(len(dataset))]
-    for e in entries:
-        image_id = e["image_id"]
-        index = index_of.get(image_id) if index_of is not None else (image_id if isinstance(image_id, int) else None)
-        if index is None or not 0 <= index < len(per_image):
-            raise ValueError("result files: image_id %r is not in the dataset" % (image_id,))
-        if labels_of is not None and e["category_id"] not in labels_of:
-            raise ValueError("result files: category_id %r is not in the dataset" % (e["category_id"],))
-        per_image[index].append(e)
+    _, per_image, labels_of = _group_entries(path_or_list, dataset)
     device = torch.device("cpu" if device is None else device)
     sizes = []
     for index in range(len(per_image)):
@@ -232,16 +251,12 @@ def load_results(path_or_list, dataset, iou_type, device=None):
     for index, es in enumerate(per_image):
         W, H = sizes[index]
         if es and all("bbox" in e for e in es):
-            boxes = torch.tensor([e["bbox"] for e in es], dtype=torch.float32).reshape(-1, 4)
-            boxlist = BoxList(boxes, (W, H), mode="xywh").convert("xyxy")
+            boxes, mode = torch.tensor([e["bbox"] for e in es], dtype=torch.float32).reshape(-1, 4), "xywh"
         elif iou_type == "bbox" and es:
             raise ValueError("result files: a bbox entry without `bbox` (image %r)" % (es[0]["image_id"],))
         else:
-            boxlist = BoxList(torch.tensor([[0.0, 0.0, W - 1.0, H - 1.0]] * len(es)).reshape(-1, 4), (W, H), mode="xyxy")
-        boxlist.add_field("scores", torch.tensor([e["score"] for e in es], dtype=torch.float32))
-        cats = [e["category_id"] for e in es]
-        boxlist.add_field("labels", torch.tensor(cats if labels_of is None else [labels_of[c] for c in cats], dtype=torch.int64))
-        boxlist = boxlist.to(device)
+            boxes, mode = torch.tensor([[0.0, 0.0, W - 1.0, H - 1.0]] * len(es)).reshape(-1, 4), "xyxy"
+        boxlist = _scored_boxlist(boxes, (W, H), mode, es, labels_of).to(device)
         if rle is not None:                          # the image's slice of the file's runs
             a, b = starts[first], starts[first + len(es)]
             boxlist.add_field("mask", RLEMasks(rle[0][a:b], rle[1][first:first + len(es) + 1] - a, (W, H)))
@@ -257,7 +272,7 @@ def evaluate_result_files(dataset, files, output_folder=None, batch=8, device="c
     masks of segm.json go from runs to bit rows there (_C.mask_pack_rle), no plane is laid out.  -> the COCOResults of
     finish_coco, which also logs the tables and, with `output_folder`, writes coco_results.pth / coco_results.txt.
     `keypoints` raises NotImplementedError: keypoints.json is scored by keypoint_oks.evaluate_keypoint_file."""
-    from . import COCOStyleEvaluator, _groundtruth, finish_coco
+    from . import finish_coco
 
     if "keypoints" in files:
         raise NotImplementedError("keypoints.json is scored by keypoint_oks.evaluate_keypoint_file (tools/evaluate_keypoints.py), "
@@ -266,15 +281,11 @@ def evaluate_result_files(dataset, files, output_folder=None, batch=8, device="c
     unknown = sorted(set(files) - set(iou_types))
     if unknown or not iou_types:
         raise ValueError("evaluate_result_files: expected files for bbox and / or segm, got %s" % sorted(files))
-    num_classes = getattr(dataset, "num_classes", None) or 81
+    num_classes = _num_classes(dataset, 81)
     device = torch.device(device)
     merged = COCOStyleEvaluator(iou_types, num_classes)
     for t in iou_types:
-        predictions = load_results(files[t], dataset, t, device)
-        evaluator = COCOStyleEvaluator((t,), num_classes)
-        for i in range(0, len(predictions), batch):
-            preds = predictions[i:i + batch]
-            evaluator.update(preds, [_groundtruth(dataset, j).to(device) for j in range(i, i + len(preds))])
+        evaluator = _feed(COCOStyleEvaluator((t,), num_classes), load_results(files[t], dataset, t, device), dataset, batch, device)
         merged.records[t] = evaluator.records[t]
         merged.num_images, merged.num_groundtruths = evaluator.num_images, evaluator.num_groundtruths
         merged.num_detections = max(merged.num_detections, evaluator.num_detections)

@@ -8,7 +8,7 @@ The rules are a restatement of pycocotools.cocoeval (evaluateImg, accumulate, su
 code.  It has NOT been checked against pycocotools, which is not available where this project is built and tested;
 tests/eval_refs.py is the literal, loop-by-loop form everything here is pinned to.
 """
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -21,7 +21,58 @@ IOU_THRS = np.linspace(0.5, 0.95, 10)
 REC_THRS = np.linspace(0.0, 1.0, 101)
 AREA_RNGS = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], dtype=np.float64)
 MAX_DETS = (1, 10, 100)
-STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
+# The statistics of an IoU type, in the order they are reported: (name, 1 precision | 0 recall, IoU threshold or None for
+# all ten, index into the evaluator's area ranges, index into its max_dets).  The keypoint evaluator has the area ranges
+# (all, medium, large) and max_dets (20,): keypoint_oks.py.
+_DETECTION_STATS = (("AP", 1, None, 0, 2), ("AP50", 1, 0.5, 0, 2), ("AP75", 1, 0.75, 0, 2), ("APs", 1, None, 1, 2),
+                    ("APm", 1, None, 2, 2), ("APl", 1, None, 3, 2), ("AR1", 0, None, 0, 0), ("AR10", 0, None, 0, 1),
+                    ("AR100", 0, None, 0, 2), ("ARs", 0, None, 1, 2), ("ARm", 0, None, 2, 2), ("ARl", 0, None, 3, 2))
+STAT_ROWS = {
+    "bbox": _DETECTION_STATS,
+    "segm": _DETECTION_STATS,
+    "keypoints": (("AP", 1, None, 0, 0), ("AP50", 1, 0.5, 0, 0), ("AP75", 1, 0.75, 0, 0), ("APm", 1, None, 1, 0),
+                  ("APl", 1, None, 2, 0), ("AR", 0, None, 0, 0), ("AR50", 0, 0.5, 0, 0), ("AR75", 0, 0.75, 0, 0),
+                  ("ARm", 0, None, 1, 0), ("ARl", 0, None, 2, 0)),
+}
+STAT_NAMES = tuple(row[0] for row in STAT_ROWS["bbox"])
+_MATCH_MODE = {"bbox": _C.EVAL_COCO_BBOX, "segm": _C.EVAL_COCO_SEGM, "keypoints": _C.EVAL_COCO_BBOX}    # of _C.eval_match
+
+
+Batch = namedtuple("Batch", "preds tgts dt_img gt_img dt_box gt_box dt_label gt_label dt_score gt_ignore counts")
+
+
+def flatten_batch(predictions, targets, ignore_field="iscrowd", resize=True, first_image=0, num_classes=None):
+    """Two lists of BoxList (one per image) -> a Batch, everything on the first target's device (no targets: the CPU):
+    preds / tgts, the images' BoxLists in xyxy, a prediction resized to its target's size when `resize`; dt_img / gt_img
+    int64, the image index of every row counted from `first_image`; dt_box / gt_box [n, 4]; dt_label / gt_label int64;
+    dt_score; gt_ignore bool, the targets' `ignore_field` ("iscrowd" or "difficult") != 0, False where a target lacks the
+    field; counts = (images, detections, ground truths).  ValueError: with `num_classes`, a label outside [0, num_classes)."""
+    dev = targets[0].bbox.device if targets else torch.device("cpu")
+    preds, tgts = [], []
+    for pred, tgt in zip(predictions, targets):
+        tgt = tgt.convert("xyxy")
+        if resize and tuple(pred.size) != tuple(tgt.size):
+            pred = pred.resize(tgt.size)
+        preds.append(pred.convert("xyxy").to(dev))
+        tgts.append(tgt)
+    n_dt, n_gt = [len(p) for p in preds], [len(t) for t in tgts]
+    i64 = dict(dtype=torch.int64, device=dev)
+    img = torch.arange(len(preds), **i64) + first_image
+    dt_img, gt_img = img.repeat_interleave(torch.tensor(n_dt, **i64)), img.repeat_interleave(torch.tensor(n_gt, **i64))
+    cat = lambda ts, **kw: torch.cat(ts) if ts else torch.zeros((0,), **kw)  # noqa: E731
+    dt_box = cat([p.bbox for p in preds]).reshape(-1, 4)
+    gt_box = cat([t.bbox for t in tgts]).reshape(-1, 4)
+    dt_label = cat([p.get_field("labels").to(**i64) for p in preds], **i64)
+    gt_label = cat([t.get_field("labels").to(**i64) for t in tgts], **i64)
+    dt_score = cat([p.get_field("scores").reshape(-1) for p in preds], device=dev)
+    gt_ignore = cat([(t.get_field(ignore_field).to(dev) != 0) if t.has_field(ignore_field)
+                     else torch.zeros((len(t),), dtype=torch.bool, device=dev) for t in tgts], dtype=torch.bool, device=dev)
+    if num_classes is not None:
+        for name, lab in (("prediction", dt_label), ("target", gt_label)):
+            if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= num_classes):
+                raise ValueError("%s labels must lie in [0, %d), got %d .. %d" % (name, num_classes, int(lab.min()), int(lab.max())))
+    return Batch(preds, tgts, dt_img, gt_img, dt_box, gt_box, dt_label, gt_label, dt_score, gt_ignore,
+                 (len(preds), sum(n_dt), sum(n_gt)))
 
 
 def build_problems(dt_img, dt_label, dt_score, gt_img, gt_label, num_classes, max_dets=MAX_DETS[-1]):
@@ -155,65 +206,50 @@ class COCOStyleEvaluator(object):
         to bit rows without a plane.  Targets carry `labels` and may carry `masks` (either SegmentationMask mode, or an
         RLEMasks), `iscrowd` and `area`."""
         assert len(predictions) == len(targets), "one prediction per target"
+        self._check_fields(predictions, targets)
         segm = "segm" in self.iou_types
-        dev = targets[0].bbox.device if targets else torch.device("cpu")
-        preds, tgts = [], []
-        for pred, tgt in zip(predictions, targets):
-            tgt = tgt.convert("xyxy")
-            if tuple(pred.size) != tuple(tgt.size):
-                pred = pred.resize(tgt.size)
-            preds.append(pred.convert("xyxy").to(dev))
-            tgts.append(tgt)
-        n_dt, n_gt = [len(p) for p in preds], [len(t) for t in tgts]
-        i64 = dict(dtype=torch.int64, device=dev)
-        img = torch.arange(len(preds), **i64) + self.num_images
-        dt_img, gt_img = img.repeat_interleave(torch.tensor(n_dt, **i64)), img.repeat_interleave(torch.tensor(n_gt, **i64))
-        cat = lambda ts, **kw: torch.cat(ts) if ts else torch.zeros((0,), **kw)  # noqa: E731
-        dt_box = cat([p.bbox for p in preds]).reshape(-1, 4)
-        gt_box = cat([t.bbox for t in tgts]).reshape(-1, 4)
-        dt_label = cat([p.get_field("labels").to(**i64) for p in preds], **i64)
-        gt_label = cat([t.get_field("labels").to(**i64) for t in tgts], **i64)
-        dt_score = cat([p.get_field("scores").reshape(-1) for p in preds], device=dev)
-        gt_crowd = cat([(t.get_field("iscrowd").to(dev) != 0) if t.has_field("iscrowd") else torch.zeros((len(t),), dtype=torch.bool, device=dev)
-                        for t in tgts], dtype=torch.bool, device=dev)
-        for name, lab in (("prediction", dt_label), ("target", gt_label)):
-            if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= self.num_classes):
-                raise ValueError("%s labels must lie in [0, %d), got %d .. %d" % (name, self.num_classes, int(lab.min()), int(lab.max())))
-        self.num_images += len(preds)
-        self.num_detections += sum(n_dt)
-        self.num_groundtruths += sum(n_gt)
-        pr = build_problems(dt_img, dt_label, dt_score, gt_img, gt_label, self.num_classes)
+        b = flatten_batch(predictions, targets, "iscrowd", True, self.num_images, self.num_classes)
+        self.num_images += b.counts[0]
+        self.num_detections += b.counts[1]        # before the cut to max_dets per problem
+        self.num_groundtruths += b.counts[2]
+        pr = build_problems(b.dt_img, b.dt_label, b.dt_score, b.gt_img, b.gt_label, self.num_classes, self.max_dets[-1])
         do, go = pr["dt_order"], pr["gt_order"]
-        has_masks = [t.has_field("masks") for t in tgts]
         gt_pack = dt_pack = None
-        if segm or needs_mask_area(tgts):    # planes, or their pixel counts
-            gt_planes = groundtruth_planes(tgts, dev)
-            if segm and not all(m or len(t) == 0 for t, m in zip(tgts, has_masks)):
+        if segm or needs_mask_area(b.tgts):    # planes, or their pixel counts
+            gt_planes = groundtruth_planes(b.tgts, b.gt_box.device)
+            if segm and not all(t.has_field("masks") or len(t) == 0 for t in b.tgts):
                 raise ValueError("segm evaluation needs ground-truth masks")
             gt_pack = _pack_masks(gt_planes)
         if segm:
-            dt_pack = _pack_masks(self._prediction_planes(preds))
-        gt_area = groundtruth_area(tgts, gt_box, gt_pack)
+            dt_pack = _pack_masks(self._prediction_planes(b.preds))
+        gt_area = groundtruth_area(b.tgts, b.gt_box, gt_pack)
         offs = (pr["dt_offset"], pr["gt_offset"], pr["iou_offset"])
         thrs, rngs = torch.from_numpy(self.iou_thrs), torch.from_numpy(self.area_rngs)
         for iou_type in self.iou_types:
-            if iou_type == "bbox":
-                iou = _C.eval_iou(_C.EVAL_COCO_BBOX, *offs, pr["total_pairs"], dt_boxes=dt_box[do], gt_boxes=gt_box[go],
-                                  gt_crowd=gt_crowd[go])
-                dt_wh = (dt_box[:, 2:] - dt_box[:, :2]) + 1
-                dt_area = (dt_wh[:, 0].to(torch.float64) * dt_wh[:, 1].to(torch.float64))[do]
-            else:
-                dpk = (dt_pack[0], dt_pack[1][do], dt_pack[2][do], dt_pack[4][do])
-                gpk = (gt_pack[0], gt_pack[1][go], gt_pack[2][go], gt_pack[4][go])
-                counts = _C.mask_pair_counts(dpk, gpk, *offs, pr["total_pairs"])
-                iou = _C.eval_iou(_C.EVAL_COCO_SEGM, *offs, pr["total_pairs"], counts=counts, dt_area=dt_pack[3][do],
-                                  gt_area=gt_pack[3][go], gt_crowd=gt_crowd[go])
-                dt_area = dt_pack[3][do].to(torch.float64)
-            code = _C.EVAL_COCO_BBOX if iou_type == "bbox" else _C.EVAL_COCO_SEGM
-            dtm, dti, gti = _C.eval_match(code, iou, *offs, pr["counts_host"], gt_crowd[go], thrs, dt_area=dt_area,
-                                          gt_area=gt_area[go], area_rngs=rngs)
-            self._keep(iou_type, pr, dt_score[do].to(torch.float64).cpu().numpy(), dtm.cpu().numpy(), dti.cpu().numpy(),
+            iou, dt_area, match_area = self._similarity(iou_type, b, pr, offs, gt_area, dt_pack, gt_pack)
+            dtm, dti, gti = _C.eval_match(_MATCH_MODE[iou_type], iou, *offs, pr["counts_host"], b.gt_ignore[go], thrs,
+                                          dt_area=dt_area, gt_area=match_area[go], area_rngs=rngs)
+            self._keep(iou_type, pr, b.dt_score[do].to(torch.float64).cpu().numpy(), dtm.cpu().numpy(), dti.cpu().numpy(),
                        gti.cpu().numpy())
+
+    def _check_fields(self, predictions, targets):
+        """what a subclass requires of the BoxLists before anything is computed"""
+
+    def _similarity(self, iou_type, b, pr, offs, gt_area, dt_pack, gt_pack):
+        """-> (the fp64 similarities of every problem's pairs [total_pairs], the detections' areas in problem order, the
+        ground truths' areas the matching takes, in input order).  b: the Batch; pr: its problems; offs: their offsets"""
+        do, go = pr["dt_order"], pr["gt_order"]
+        if iou_type == "bbox":
+            iou = _C.eval_iou(_C.EVAL_COCO_BBOX, *offs, pr["total_pairs"], dt_boxes=b.dt_box[do], gt_boxes=b.gt_box[go],
+                              gt_crowd=b.gt_ignore[go])
+            dt_wh = (b.dt_box[:, 2:] - b.dt_box[:, :2]) + 1
+            return iou, (dt_wh[:, 0].to(torch.float64) * dt_wh[:, 1].to(torch.float64))[do], gt_area
+        dpk = (dt_pack[0], dt_pack[1][do], dt_pack[2][do], dt_pack[4][do])
+        gpk = (gt_pack[0], gt_pack[1][go], gt_pack[2][go], gt_pack[4][go])
+        counts = _C.mask_pair_counts(dpk, gpk, *offs, pr["total_pairs"])
+        iou = _C.eval_iou(_C.EVAL_COCO_SEGM, *offs, pr["total_pairs"], counts=counts, dt_area=dt_pack[3][do],
+                          gt_area=gt_pack[3][go], gt_crowd=b.gt_ignore[go])
+        return iou, dt_pack[3][do].to(torch.float64), gt_area
 
     def _prediction_planes(self, preds):
         """-> per image a [n_i, H_i, W_i] uint8 / bool tensor, or the prediction's RLEMasks as it is"""
@@ -265,7 +301,7 @@ class COCOStyleEvaluator(object):
 
     def summarize(self):
         self.accumulate()
-        self.stats = OrderedDict((t, summarize(self.eval[t], self.iou_thrs, self.max_dets)) for t in self.iou_types)
+        self.stats = OrderedDict((t, summarize(self.eval[t], self.iou_thrs, STAT_ROWS[t])) for t in self.iou_types)
         return self.stats
 
 
@@ -308,9 +344,9 @@ def accumulate(records, num_classes, iou_thrs=IOU_THRS, rec_thrs=REC_THRS, num_a
     return {"precision": precision, "recall": recall}
 
 
-def summarize(ev, iou_thrs=IOU_THRS, max_dets=MAX_DETS):
-    """-> the 12 numbers (STAT_NAMES): the mean of the cells greater than -1, or -1 when there are none"""
-    def stat(ap, thr=None, area=0, m=len(max_dets) - 1):
+def summarize(ev, iou_thrs=IOU_THRS, rows=STAT_ROWS["bbox"]):
+    """-> one number per row of `rows` (STAT_ROWS): the mean of the cells greater than -1, or -1 when there are none"""
+    def stat(ap, thr, area, m):
         s = ev["precision"] if ap else ev["recall"]
         if thr is not None:
             s = s[np.nonzero(np.isclose(iou_thrs, thr))[0]]
@@ -318,5 +354,23 @@ def summarize(ev, iou_thrs=IOU_THRS, max_dets=MAX_DETS):
         s = s[s > -1]
         return float(np.mean(s)) if s.size else -1.0
 
-    return np.array([stat(1), stat(1, 0.5), stat(1, 0.75), stat(1, area=1), stat(1, area=2), stat(1, area=3),
-                     stat(0, m=0), stat(0, m=1), stat(0, m=2), stat(0, area=1), stat(0, area=2), stat(0, area=3)])
+    return np.array([stat(*row[1:]) for row in rows])
+
+
+# ------------------------------------------------------------------------------------------------ scoring stored predictions
+def _groundtruth(dataset, index):
+    return dataset.get_groundtruth(index) if hasattr(dataset, "get_groundtruth") else dataset[index][1]
+
+
+def _num_classes(dataset, default):
+    return getattr(dataset, "num_classes", None) or default
+
+
+def _feed(evaluator, predictions, dataset, batch, device=None):
+    """`predictions` (one per image, in dataset order) go to evaluator.update `batch` images at a time, against the
+    dataset's ground truth moved to `device` (None: where the batch's first prediction lives) -> evaluator"""
+    for i in range(0, len(predictions), batch):
+        preds = list(predictions[i:i + batch])
+        dev = preds[0].bbox.device if device is None else device
+        evaluator.update(preds, [_groundtruth(dataset, j).to(dev) for j in range(i, i + len(preds))])
+    return evaluator

@@ -17,21 +17,21 @@ These are names of their own: the generic entry points (`evaluate`, `COCOStyleEv
 tools/evaluate_keypoints.py are the way in.
 """
 import os
-from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from maskrcnn_benchmark import _C, _eval_cpu
-from maskrcnn_benchmark.structures.bounding_box import BoxList
 from maskrcnn_benchmark.structures.keypoint import PersonKeypoints
 
 from . import coco_style
+from .coco_results import _group_entries, _scored_boxlist
+from .coco_style import _feed, _num_classes
 
 IOU_THRS, REC_THRS = coco_style.IOU_THRS, coco_style.REC_THRS
 AREA_RNGS = np.array([[0, 1e10], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], dtype=np.float64)      # all, medium, large
 MAX_DETS = (20,)
-STAT_NAMES = ("AP", "AP50", "AP75", "APm", "APl", "AR", "AR50", "AR75", "ARm", "ARl")
+STAT_NAMES = tuple(row[0] for row in coco_style.STAT_ROWS["keypoints"])
 COCO_PERSON_SIGMAS = _eval_cpu.COCO_PERSON_SIGMAS
 
 
@@ -47,6 +47,13 @@ def _keypoint_tensor(boxlist, K, dev):
     return kp
 
 
+def _keypoints_of(boxlists, K, dev):
+    """the keypoints of a batch's BoxLists, one after the other: fp32 [n, K, 3]; an empty BoxList needs no field"""
+    f32 = dict(dtype=torch.float32, device=dev)
+    parts = [_keypoint_tensor(x, K, dev) if len(x) else torch.zeros((0, K, 3), **f32) for x in boxlists]
+    return torch.cat(parts) if parts else torch.zeros((0, K, 3), **f32)
+
+
 class KeypointOKSEvaluator(coco_style.COCOStyleEvaluator):
     """evaluator = KeypointOKSEvaluator(num_classes, sigmas); evaluator.update(predictions, targets) per batch;
     evaluator.summarize() -> {"keypoints": the 10 numbers AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl}.
@@ -54,7 +61,11 @@ class KeypointOKSEvaluator(coco_style.COCOStyleEvaluator):
     area ranges, the cut to 20 detections and the ten statistics.
 
     sigmas: the per-keypoint constants, fp64 [K] (default: the 17 of the COCO person table).  Labels are the contiguous
-    ones (1 .. num_classes - 1).  At most 20 detections per (image, category) are matched."""
+    ones (1 .. num_classes - 1).  At most 20 detections per (image, category) are matched.
+
+    update(predictions, targets): two lists of BoxList (one per image), on the device or the CPU.  Predictions carry
+    `scores`, `labels` and `keypoints` [n, K, 3] (a Keypoints or a tensor; the third column is not read); targets carry
+    `labels`, `keypoints` (third column: the visibility flag) and may carry `iscrowd`, `area` and `masks`."""
 
     iou_types = ("keypoints",)
 
@@ -68,112 +79,45 @@ class KeypointOKSEvaluator(coco_style.COCOStyleEvaluator):
         self.num_images = self.num_detections = self.num_groundtruths = 0
         self.eval = {}
 
-    # ------------------------------------------------------------------ per batch
-    def update(self, predictions, targets):
-        """predictions, targets: two lists of BoxList (one per image), on the device or the CPU.  Predictions carry
-        `scores`, `labels` and `keypoints` [n, K, 3] (a Keypoints or a tensor; the third column is not read); targets carry
-        `labels`, `keypoints` (third column: the visibility flag) and may carry `iscrowd`, `area` and `masks`."""
-        assert len(predictions) == len(targets), "one prediction per target"
-        K = self.sigmas.size
-        dev = targets[0].bbox.device if targets else torch.device("cpu")
-        preds, tgts = [], []
+    # ------------------------------------------------------------------ per batch: its part of COCOStyleEvaluator.update
+    def _check_fields(self, predictions, targets):
         for pred, tgt in zip(predictions, targets):
-            tgt = tgt.convert("xyxy")
-            if tuple(pred.size) != tuple(tgt.size):
-                pred = pred.resize(tgt.size)
             if len(tgt) and not tgt.has_field("keypoints"):
                 raise ValueError("keypoint evaluation needs ground-truth keypoints")
             if len(pred) and not pred.has_field("keypoints"):
                 raise ValueError("keypoint evaluation needs predictions with a `keypoints` field")
-            preds.append(pred.to(dev))
-            tgts.append(tgt)
-        n_dt, n_gt = [len(p) for p in preds], [len(t) for t in tgts]
-        i64 = dict(dtype=torch.int64, device=dev)
-        img = torch.arange(len(preds), **i64) + self.num_images
-        dt_img, gt_img = img.repeat_interleave(torch.tensor(n_dt, **i64)), img.repeat_interleave(torch.tensor(n_gt, **i64))
-        cat = lambda ts, **kw: torch.cat(ts) if ts else torch.zeros((0,), **kw)  # noqa: E731
-        f32 = dict(dtype=torch.float32, device=dev)
-        dt_kp = cat([_keypoint_tensor(p, K, dev) if len(p) else torch.zeros((0, K, 3), **f32) for p in preds], **f32).reshape(-1, K, 3)
-        gt_kp = cat([_keypoint_tensor(t, K, dev) if len(t) else torch.zeros((0, K, 3), **f32) for t in tgts], **f32).reshape(-1, K, 3)
-        gt_box = cat([t.bbox for t in tgts]).reshape(-1, 4)
-        dt_label = cat([p.get_field("labels").to(**i64) for p in preds], **i64)
-        gt_label = cat([t.get_field("labels").to(**i64) for t in tgts], **i64)
-        dt_score = cat([p.get_field("scores").reshape(-1) for p in preds], device=dev)
-        gt_crowd = cat([(t.get_field("iscrowd").to(dev) != 0) if t.has_field("iscrowd") else torch.zeros((len(t),), dtype=torch.bool, device=dev)
-                        for t in tgts], dtype=torch.bool, device=dev)
-        for name, lab in (("prediction", dt_label), ("target", gt_label)):
-            if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= self.num_classes):
-                raise ValueError("%s labels must lie in [0, %d), got %d .. %d" % (name, self.num_classes, int(lab.min()), int(lab.max())))
-        self.num_images += len(preds)
-        self.num_detections += sum(n_dt)
-        self.num_groundtruths += sum(n_gt)
-        pr = coco_style.build_problems(dt_img, dt_label, dt_score, gt_img, gt_label, self.num_classes, max_dets=MAX_DETS[-1])
-        do, go = pr["dt_order"], pr["gt_order"]
-        gt_pack = coco_style._pack_masks(coco_style.groundtruth_planes(tgts, dev)) if coco_style.needs_mask_area(tgts) else None
-        gt_area = coco_style.groundtruth_area(tgts, gt_box, gt_pack)
-        offs = (pr["dt_offset"], pr["gt_offset"], pr["iou_offset"])
-        oks, dt_area = _C.eval_oks(dt_kp[do], gt_kp[go], gt_box[go], gt_area[go], self.sigmas, *offs, pr["total_pairs"])
-        # no visible keypoint and no crowd: ignored in every range and not matched again (area -1 lies outside every range)
-        unlabelled = ((gt_kp[:, :, 2] > 0).sum(dim=1) == 0) & ~gt_crowd
-        match_area = torch.where(unlabelled, torch.full_like(gt_area, -1.0), gt_area)
-        dtm, dti, gti = _C.eval_match(_C.EVAL_COCO_BBOX, oks, *offs, pr["counts_host"], gt_crowd[go], torch.from_numpy(self.iou_thrs),
-                                      dt_area=dt_area, gt_area=match_area[go], area_rngs=torch.from_numpy(self.area_rngs))
-        self._keep("keypoints", pr, dt_score[do].to(torch.float64).cpu().numpy(), dtm.cpu().numpy(), dti.cpu().numpy(),
-                   gti.cpu().numpy())
 
-    # ------------------------------------------------------------------ once per evaluation
-    def summarize(self):
-        self.accumulate()
-        self.stats = OrderedDict([("keypoints", summarize(self.eval["keypoints"], self.iou_thrs))])
-        return self.stats
+    def _similarity(self, iou_type, b, pr, offs, gt_area, dt_pack, gt_pack):
+        K, dev = self.sigmas.size, b.gt_box.device
+        do, go = pr["dt_order"], pr["gt_order"]
+        dt_kp, gt_kp = _keypoints_of(b.preds, K, dev), _keypoints_of(b.tgts, K, dev)
+        oks, dt_area = _C.eval_oks(dt_kp[do], gt_kp[go], b.gt_box[go], gt_area[go], self.sigmas, *offs, pr["total_pairs"])
+        # no visible keypoint and no crowd: ignored in every range and not matched again (area -1 lies outside every range)
+        unlabelled = ((gt_kp[:, :, 2] > 0).sum(dim=1) == 0) & ~b.gt_ignore
+        return oks, dt_area, torch.where(unlabelled, torch.full_like(gt_area, -1.0), gt_area)
 
 
 def summarize(ev, iou_thrs=IOU_THRS):
     """-> the 10 numbers (STAT_NAMES): the mean of the cells greater than -1, or -1 when there are none"""
-    def stat(ap, thr=None, area=0):
-        s = ev["precision"] if ap else ev["recall"]
-        if thr is not None:
-            s = s[np.nonzero(np.isclose(iou_thrs, thr))[0]]
-        s = s[:, :, :, area, 0] if ap else s[:, :, area, 0]
-        s = s[s > -1]
-        return float(np.mean(s)) if s.size else -1.0
-
-    return np.array([stat(1), stat(1, 0.5), stat(1, 0.75), stat(1, area=1), stat(1, area=2),
-                     stat(0), stat(0, 0.5), stat(0, 0.75), stat(0, area=1), stat(0, area=2)])
+    return coco_style.summarize(ev, iou_thrs, coco_style.STAT_ROWS["keypoints"])
 
 
 # ------------------------------------------------------------------------------------------------ keypoints.json
 def load_keypoint_results(path_or_list, dataset, device=None):
     """A `keypoints.json` result file (a path, or its list of entries) -> a list of BoxList in dataset order, what
     KeypointOKSEvaluator.update takes: the inverse of coco_results.keypoint_entries, with the id and label maps of
-    load_results (entries grouped by `image_id` through the inverse of `id_to_img_map`, the file's order kept inside an
-    image; labels through `json_category_id_to_contiguous_id`; a dataset without these maps uses the index and the label).
+    load_results (coco_results._group_entries; the file's order is kept inside an image).
     `keypoints` is the flat list of 3 K numbers and becomes a PersonKeypoints field [n, K, 3]; the box is the keypoints'
     extents (min x, min y, max x, max y), as pycocotools' loadRes makes it.  ValueError: an unknown image id or category id,
     a keypoint list whose length is no multiple of 3 or differs inside the file."""
-    from .coco_results import _read_entries
-
-    entries = _read_entries(path_or_list)
-    ids = getattr(dataset, "id_to_img_map", None)
-    index_of = {v: k for k, v in ids.items()} if ids is not None else None
-    labels_of = getattr(dataset, "json_category_id_to_contiguous_id", None)
-    if labels_of is None and getattr(dataset, "contiguous_category_id_to_json_id", None) is not None:
-        labels_of = {v: k for k, v in dataset.contiguous_category_id_to_json_id.items()}
-    per_image = [[] for _ in range(len(dataset))]
+    entries, per_image, labels_of = _group_entries(path_or_list, dataset)
     K = None
     for e in entries:
-        image_id = e["image_id"]
-        index = index_of.get(image_id) if index_of is not None else (image_id if isinstance(image_id, int) else None)
-        if index is None or not 0 <= index < len(per_image):
-            raise ValueError("result files: image_id %r is not in the dataset" % (image_id,))
-        if labels_of is not None and e["category_id"] not in labels_of:
-            raise ValueError("result files: category_id %r is not in the dataset" % (e["category_id"],))
         n = len(e.get("keypoints", ()))
         if n == 0 or n % 3 or (K is not None and n != 3 * K):
             raise ValueError("result files: %d keypoint numbers (image %r): expected the same multiple of 3 in every entry"
-                             % (n, image_id))
+                             % (n, e["image_id"]))
         K = n // 3
-        per_image[index].append(e)
     device = torch.device("cpu" if device is None else device)
     K = 17 if K is None else K
     out = []
@@ -186,10 +130,7 @@ def load_keypoint_results(path_or_list, dataset, device=None):
             boxes = torch.cat([lo, hi], dim=1)
         else:
             boxes = torch.zeros((0, 4), dtype=torch.float32)
-        boxlist = BoxList(boxes, (W, H), mode="xyxy")
-        boxlist.add_field("scores", torch.tensor([e["score"] for e in es], dtype=torch.float32))
-        cats = [e["category_id"] for e in es]
-        boxlist.add_field("labels", torch.tensor(cats if labels_of is None else [labels_of[c] for c in cats], dtype=torch.int64))
+        boxlist = _scored_boxlist(boxes, (W, H), "xyxy", es, labels_of)
         boxlist.add_field("keypoints", PersonKeypoints(kp, (W, H)))
         out.append(boxlist.to(device))
     return out
@@ -200,14 +141,11 @@ def evaluate_keypoint_file(dataset, path_or_list, output_folder=None, batch=8, d
     """Score a saved `keypoints.json` (a path, or its list of entries) against `dataset`'s ground truth: one
     KeypointOKSEvaluator fed `batch` images at a time on `device` -> the COCOResults of finish_coco, which also logs the
     table and, with `output_folder`, writes coco_results.pth / coco_results.txt."""
-    from . import _groundtruth, finish_coco
+    from . import finish_coco
 
     device = torch.device(device)
     predictions = load_keypoint_results(path_or_list, dataset, device)
-    evaluator = KeypointOKSEvaluator(getattr(dataset, "num_classes", None) or 2, sigmas)
-    for i in range(0, len(predictions), batch):
-        preds = predictions[i:i + batch]
-        evaluator.update(preds, [_groundtruth(dataset, j).to(device) for j in range(i, i + len(preds))])
+    evaluator = _feed(KeypointOKSEvaluator(_num_classes(dataset, 2), sigmas), predictions, dataset, batch, device)
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
     return finish_coco(evaluator, output_folder, expected_results, expected_results_sigma_tol)

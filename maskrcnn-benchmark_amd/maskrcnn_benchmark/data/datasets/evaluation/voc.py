@@ -8,39 +8,25 @@ order; the reference's `argsort()[::-1]` leaves the order of ties to numpy's qui
 import os
 
 import numpy as np
-import torch
 
 from maskrcnn_benchmark import _C
 
-from .coco_style import build_problems
+from .coco_style import build_problems, flatten_batch
 
 
 def voc_matches(gt_boxlists, pred_boxlists, iou_thresh=0.5):
     """-> (n_pos, score, match): dicts by label; score[l] / match[l] hold the detections of label l image after image, by
     score descending inside an image; match values 1 (true positive), 0 (false positive), -1 (a difficult ground truth)"""
     assert len(gt_boxlists) == len(pred_boxlists), "Length of gt and pred lists need to be same."
-    dev = gt_boxlists[0].bbox.device if gt_boxlists else torch.device("cpu")
-    i64 = dict(dtype=torch.int64, device=dev)
-    preds = [p.convert("xyxy").to(dev) for p in pred_boxlists]
-    gts = [g.convert("xyxy") for g in gt_boxlists]
-    img = torch.arange(len(preds), **i64)
-    dt_img = img.repeat_interleave(torch.tensor([len(p) for p in preds], **i64))
-    gt_img = img.repeat_interleave(torch.tensor([len(g) for g in gts], **i64))
-    cat = lambda ts, **kw: torch.cat(ts) if ts else torch.zeros((0,), **kw)  # noqa: E731
-    dt_box, gt_box = cat([p.bbox for p in preds]).reshape(-1, 4), cat([g.bbox for g in gts]).reshape(-1, 4)
-    dt_label = cat([p.get_field("labels").to(**i64) for p in preds], **i64)
-    gt_label = cat([g.get_field("labels").to(**i64) for g in gts], **i64)
-    dt_score = cat([p.get_field("scores").reshape(-1) for p in preds], device=dev)
-    difficult = cat([(g.get_field("difficult").to(dev) != 0) if g.has_field("difficult")
-                     else torch.zeros((len(g),), dtype=torch.bool, device=dev) for g in gts], dtype=torch.bool, device=dev)
-    C = int(max(int(dt_label.max()) if dt_label.numel() else 0, int(gt_label.max()) if gt_label.numel() else 0)) + 1
-    pr = build_problems(dt_img, dt_label, dt_score, gt_img, gt_label, C, max_dets=2 ** 31 - 1)
+    b = flatten_batch(pred_boxlists, gt_boxlists, "difficult", resize=False)       # no class range: the largest label seen
+    C = int(max(int(b.dt_label.max()) if b.dt_label.numel() else 0, int(b.gt_label.max()) if b.gt_label.numel() else 0)) + 1
+    pr = build_problems(b.dt_img, b.dt_label, b.dt_score, b.gt_img, b.gt_label, C, max_dets=2 ** 31 - 1)
     do, go = pr["dt_order"], pr["gt_order"]
     offs = (pr["dt_offset"], pr["gt_offset"], pr["iou_offset"])
-    iou = _C.eval_iou(_C.EVAL_VOC, *offs, pr["total_pairs"], dt_boxes=dt_box[do], gt_boxes=gt_box[go])
-    m = _C.eval_match(_C.EVAL_VOC, iou, *offs, pr["counts_host"], difficult[go], [float(iou_thresh)]).cpu().numpy()
-    scores = dt_score[do].cpu().numpy()
-    hard = difficult[go].cpu().numpy()
+    iou = _C.eval_iou(_C.EVAL_VOC, *offs, pr["total_pairs"], dt_boxes=b.dt_box[do], gt_boxes=b.gt_box[go])
+    m = _C.eval_match(_C.EVAL_VOC, iou, *offs, pr["counts_host"], b.gt_ignore[go], [float(iou_thresh)]).cpu().numpy()
+    scores = b.dt_score[do].cpu().numpy()
+    hard = b.gt_ignore[go].cpu().numpy()
     d = np.concatenate([[0], np.cumsum(pr["D"])])
     g = np.concatenate([[0], np.cumsum(pr["G"])])
     n_pos, score, match = {}, {}, {}

@@ -14,6 +14,7 @@ import torch
 from maskrcnn_benchmark.data.datasets.evaluation import COCOStyleEvaluator, check_scope, dataset_style, finish_coco
 from maskrcnn_benchmark.data.datasets.evaluation import evaluate as evaluate_predictions
 from maskrcnn_benchmark.data.datasets.evaluation.coco_results import COCOResultsWriter
+from maskrcnn_benchmark.data.datasets.evaluation.coco_style import _num_classes
 from maskrcnn_benchmark.data.datasets.evaluation.keypoint_oks import KeypointOKSEvaluator
 from maskrcnn_benchmark.utils.comm import get_world_size
 
@@ -76,7 +77,7 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     dataset = data_loader.dataset
     logger.info("Start evaluation on {} dataset({} images).".format(dataset_name, len(dataset)))
     streaming = dataset_style(dataset) == "coco"
-    evaluator = writer = kp_evaluator = None
+    evaluators, writer = [], None
     if keypoint_oks and (not streaming or box_only or bbox_aug):
         raise NotImplementedError("inference(keypoint_oks=True): keypoints are scored for COCO-shaped datasets and detections "
                                   "only (not box_only proposals, not under box augmentation)")
@@ -85,9 +86,9 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
                                   "only (not box_only proposals)")
     if streaming and evaluate:
         check_scope(box_only, iou_types)
-        evaluator = COCOStyleEvaluator(iou_types, getattr(dataset, "num_classes", None) or 81)
+        evaluators = [COCOStyleEvaluator(iou_types, _num_classes(dataset, 81))]
         if keypoint_oks:
-            kp_evaluator = KeypointOKSEvaluator(getattr(dataset, "num_classes", None) or 2)
+            evaluators.append(KeypointOKSEvaluator(_num_classes(dataset, 2)))
     if streaming and output_folder and not box_only:
         writer = COCOResultsWriter(dataset, tuple(iou_types) + (("keypoints",) if keypoint_oks and "keypoints" not in iou_types else ()))
     model.eval()
@@ -107,11 +108,10 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
             model_time += time.time() - t0
             if writer is not None:
                 writer.update(output, image_ids)
-            if evaluator is not None:
+            if evaluators:
                 targets = [t.to(device) for t in targets]
-                evaluator.update(output, targets)
-                if kp_evaluator is not None:
-                    kp_evaluator.update(output, targets)
+                for evaluator in evaluators:
+                    evaluator.update(output, targets)
             elif not streaming:
                 predictions.update({i: o.to("cpu") for i, o in zip(image_ids, output)})
     total = time.time() - start
@@ -129,9 +129,8 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
         return paths
     if streaming:
         logger.info("Matched {} detections against {} ground truths of {} images".format(
-            evaluator.num_detections, evaluator.num_groundtruths, evaluator.num_images))
-        return finish_coco(evaluator if kp_evaluator is None else [evaluator, kp_evaluator], output_folder, expected_results,
-                           expected_results_sigma_tol)
+            evaluators[0].num_detections, evaluators[0].num_groundtruths, evaluators[0].num_images))
+        return finish_coco(evaluators, output_folder, expected_results, expected_results_sigma_tol)
     predictions = [predictions[i] for i in sorted(predictions)]
     if output_folder:
         torch.save(predictions, os.path.join(output_folder, "predictions.pth"))

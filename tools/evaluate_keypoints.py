@@ -14,7 +14,6 @@ The rules (include/detops.h, "Keypoint evaluation (OKS)") are a restatement of p
 it.  Not a reference tool: tools/test_net.py itself still refuses a keypoint config, the generic `keypoints` IoU type is
 not routed to OKS yet."""
 import argparse
-import logging
 import os
 import sys
 
@@ -22,9 +21,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import test_net  # noqa: E402
 
-from maskrcnn_benchmark.data import make_data_loader  # noqa: E402
+from evaluate_results import score_folder  # noqa: E402
 from maskrcnn_benchmark.data.datasets.evaluation.keypoint_oks import evaluate_keypoint_file  # noqa: E402
-from maskrcnn_benchmark.engine.bench_step import load_cfg  # noqa: E402
 
 
 def main(argv=None):
@@ -46,21 +44,8 @@ def main(argv=None):
             return test_net.main(forwarded + list(args.opts or []))
         finally:
             test_net.inference = run
-    cfg = load_cfg(args.config_file, args.opts or [])
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(levelname)s: %(message)s")
-    names = cfg.DATASETS.TEST or ("synthetic_coco",)
-    if len(names) != 1:
-        raise SystemExit("tools/evaluate_keypoints.py scores one folder against one dataset: DATASETS.TEST names %d" % len(names))
-    path = os.path.join(args.results, "keypoints.json")
-    if not os.path.exists(path):
-        raise SystemExit("no keypoints.json in %s" % args.results)
-    dataset = make_data_loader(cfg, is_train=False, length=args.images).dataset
-    out_dir = cfg.OUTPUT_DIR if cfg.OUTPUT_DIR != "." else ""
-    res = evaluate_keypoint_file(dataset, path, output_folder=args.results if out_dir else None, batch=cfg.TEST.IMS_PER_BATCH,
-                                 device=cfg.MODEL.DEVICE, expected_results=cfg.TEST.EXPECTED_RESULTS,
-                                 expected_results_sigma_tol=cfg.TEST.EXPECTED_RESULTS_SIGMA_TOL)
-    print(res)
-    return [res]
+    return score_folder("evaluate_keypoints.py", args, ("keypoints",),
+                        lambda dataset, files, **kw: evaluate_keypoint_file(dataset, files["keypoints"], **kw))
 
 
 if __name__ == "__main__":
