@@ -257,9 +257,9 @@ def mask_reference(H, W, M, dtype):
 
 
 # ------------------------------------------------------------------------------------------ encode (fp64)
-def encode64(gt, boxes, weights):
-    """BoxCoder.encode ("+1" widths) in fp64; torch tensors [..., 4]"""
-    gt, boxes = gt.double(), boxes.double()
+def encode64(gt, boxes, weights, dtype=torch.float64):
+    """BoxCoder.encode ("+1" widths) in fp64 (`dtype=torch.float32`: the same ATen composition in fp32); torch tensors [..., 4]"""
+    gt, boxes = gt.to(dtype), boxes.to(dtype)
     ew, eh = boxes[..., 2] - boxes[..., 0] + 1, boxes[..., 3] - boxes[..., 1] + 1
     ex, ey = boxes[..., 0] + 0.5 * ew, boxes[..., 1] + 0.5 * eh
     gw, gh = gt[..., 2] - gt[..., 0] + 1, gt[..., 3] - gt[..., 1] + 1
@@ -296,6 +296,25 @@ def _encode32(gt, an, weights):
     gx, gy = gt[0] + f(0.5) * gw, gt[1] + f(0.5) * gh
     return np.array([f(weights[0]) * (gx - ex) / ew, f(weights[1]) * (gy - ey) / eh, f(weights[2]) * np.log(gw / ew),
                      f(weights[3]) * np.log(gh / eh)], np.float32)
+
+
+def rpn_loss_reference(obj, box, anchors, matched, pos, neg, gt, beta, weights, A, upstream=RPN_UPSTREAM, dtype=torch.float64):
+    """fp64 autograd of the RPN losses over the sampled anchors, both / max(#sampled, 1); a sampled positive with a negative
+    matched index regresses to ground-truth row 0 -> (objectness loss, box loss, d/d objectness per level, d/d regression per
+    level).  `dtype=torch.float32`: the same ATen composition in fp32."""
+    to = [torch.from_numpy(t).to(dtype).requires_grad_() for t in obj]
+    tb = [torch.from_numpy(t).to(dtype).requires_grad_() for t in box]
+    o, b = _flatten_levels(to, tb, A)
+    tm, tp, tn = torch.from_numpy(matched), torch.from_numpy(pos), torch.from_numpy(neg)
+    mg = torch.gather(torch.from_numpy(gt), 1, tm.clamp(min=0)[:, :, None].expand(-1, -1, 4))
+    tg = encode64(mg, torch.from_numpy(anchors).unsqueeze(0), weights, dtype)
+    ns = (tp | tn).sum().clamp(min=1).to(dtype)
+    bl = smooth_l1_64(b - tg, beta).sum(-1)
+    box_loss = torch.where(tp, bl, torch.zeros_like(bl)).sum() / ns
+    bce = torch.nn.functional.binary_cross_entropy_with_logits(o, tp.to(dtype), reduction="none")
+    obj_loss = torch.where(tp | tn, bce, torch.zeros_like(bce)).sum() / ns
+    (upstream[0] * obj_loss + upstream[1] * box_loss).backward()
+    return obj_loss.item(), box_loss.item(), [t.grad.numpy() for t in to], [t.grad.numpy() for t in tb]
 
 
 @functools.lru_cache(maxsize=None)
@@ -357,19 +376,7 @@ def rpn_loss_case(name):
         for t, v in zip(list(tp) + list(tn), (90.0, -90.0, 90.0, -90.0)):
             l, y, x, a = flat[int(t)]
             obj[l][0, a, y, x] = v
-    to = [torch.from_numpy(t).double().requires_grad_() for t in obj]
-    tb = [torch.from_numpy(t).double().requires_grad_() for t in box]
-    o, b = _flatten_levels(to, tb, A)
-    tm, tp, tn = torch.from_numpy(matched), torch.from_numpy(pos), torch.from_numpy(neg)
-    mg = torch.gather(torch.from_numpy(gt), 1, tm.clamp(min=0)[:, :, None].expand(-1, -1, 4))
-    tg = encode64(mg, torch.from_numpy(anchors).unsqueeze(0), weights)
-    ns = (tp | tn).sum().clamp(min=1).double()
-    bl = smooth_l1_64(b - tg, beta).sum(-1)
-    box_loss = torch.where(tp, bl, torch.zeros_like(bl)).sum() / ns
-    bce = torch.nn.functional.binary_cross_entropy_with_logits(o, tp.double(), reduction="none")
-    obj_loss = torch.where(tp | tn, bce, torch.zeros_like(bce)).sum() / ns
-    (RPN_UPSTREAM[0] * obj_loss + RPN_UPSTREAM[1] * box_loss).backward()
-    ref = (obj_loss.item(), box_loss.item(), [t.grad.numpy() for t in to], [t.grad.numpy() for t in tb])
+    ref = rpn_loss_reference(obj, box, anchors, matched, pos, neg, gt, beta, weights, A)
     return dict(obj=obj, box=box, anchors=anchors, matched=matched, pos=pos, neg=neg, gt=gt, beta=beta, weights=weights, ref=ref)
 
 
@@ -470,21 +477,22 @@ FASTRCNN_CASES = ((1, 2, False, 1.0, 3.0), (3, 63, False, 1.0, 3.0), (5, 64, Tru
 HEAD_UPSTREAM = (1.7, 0.6)
 
 
-def fastrcnn_reference(logits, box, labels, targets, agnostic, beta, upstream):
+def fastrcnn_reference(logits, box, labels, targets, agnostic, beta, upstream, dtype=torch.float64):
     """fp64 autograd of cross-entropy + smooth-L1: rows 0 <= label < C count (and normalise), rows 0 < label < C regress;
-    class-agnostic reads columns 4..7 -> (class loss, box loss, d/d logits, d/d box)"""
+    class-agnostic reads columns 4..7 -> (class loss, box loss, d/d logits, d/d box).  `dtype=torch.float32`: the same ATen
+    composition in fp32, whose error against the fp64 result is what a bound on a new case is derived from."""
     R, C = logits.shape
-    tl = torch.from_numpy(logits).double().requires_grad_()
-    tb = torch.from_numpy(box).double().requires_grad_()
+    tl = torch.from_numpy(logits).to(dtype).requires_grad_()
+    tb = torch.from_numpy(box).to(dtype).requires_grad_()
     L = torch.from_numpy(labels)
     row = (L >= 0) & (L < C)
     fg = (L > 0) & (L < C)
-    n = row.sum().clamp(min=1).double()
+    n = row.sum().clamp(min=1).to(dtype)
     safe = torch.where(row, L, torch.zeros_like(L))
     ce = torch.logsumexp(tl, 1) - tl.gather(1, safe[:, None]).squeeze(1)
     cls = torch.where(row, ce, torch.zeros_like(ce)).sum() / n
     cols = (torch.arange(4, 8).expand(R, 4) if agnostic else 4 * torch.where(fg, L, torch.zeros_like(L))[:, None] + torch.arange(4))
-    l1 = smooth_l1_64(tb.gather(1, cols) - torch.from_numpy(targets).double(), beta).sum(1)
+    l1 = smooth_l1_64(tb.gather(1, cols) - torch.from_numpy(targets).to(dtype), beta).sum(1)
     reg = torch.where(fg, l1, torch.zeros_like(l1)).sum() / n
     (upstream[0] * cls + upstream[1] * reg).backward()
     return cls.item(), reg.item(), tl.grad.numpy(), tb.grad.numpy()
@@ -522,6 +530,21 @@ MASK_LOSS_CASES = ((1, 2, 1, 2.0), (3, 7, 14, 2.0), (5, 8, 28, 2.0), (5, 9, 17, 
 MASK_UPSTREAM = 0.8
 
 
+def mask_loss_reference(logits, labels, targets, upstream=MASK_UPSTREAM, dtype=torch.float64):
+    """fp64 autograd of the mean BCE-with-logits over the class planes of the rows 0 < label < C -> (loss, d/d logits);
+    `dtype=torch.float32`: the same ATen composition in fp32"""
+    P, C, M, _ = logits.shape
+    tl = torch.from_numpy(logits).to(dtype).requires_grad_()
+    L = torch.from_numpy(labels)
+    fg = (L > 0) & (L < C)
+    own = torch.where(fg, L, torch.zeros_like(L))[:, None, None, None].expand(-1, 1, M, M)
+    bce = torch.nn.functional.binary_cross_entropy_with_logits(tl.gather(1, own).squeeze(1), torch.from_numpy(targets).to(dtype),
+                                                               reduction="none")
+    loss = torch.where(fg[:, None, None], bce, torch.zeros_like(bce)).sum() / (fg.sum() * (M * M)).clamp(min=1).to(dtype)
+    (upstream * loss).backward()
+    return loss.item(), tl.grad.numpy()
+
+
 @functools.lru_cache(maxsize=None)
 def mask_loss_case(P, C, M, scale, no_positives=False):
     """-> inputs + ref = (loss, d/d logits) in fp64: mean BCE-with-logits over the class planes of the rows 0 < label < C"""
@@ -534,12 +557,4 @@ def mask_loss_case(P, C, M, scale, no_positives=False):
         labels[1], labels[2] = C, 0                                 # malformed, background
     if no_positives:
         labels = np.where((labels > 0) & (labels < C), 0, labels)
-    tl = torch.from_numpy(logits).double().requires_grad_()
-    L = torch.from_numpy(labels)
-    fg = (L > 0) & (L < C)
-    own = torch.where(fg, L, torch.zeros_like(L))[:, None, None, None].expand(-1, 1, M, M)
-    bce = torch.nn.functional.binary_cross_entropy_with_logits(tl.gather(1, own).squeeze(1), torch.from_numpy(targets).double(),
-                                                               reduction="none")
-    loss = torch.where(fg[:, None, None], bce, torch.zeros_like(bce)).sum() / (fg.sum() * (M * M)).clamp(min=1).double()
-    (MASK_UPSTREAM * loss).backward()
-    return dict(logits=logits, labels=labels, targets=targets, ref=(loss.item(), tl.grad.numpy()))
+    return dict(logits=logits, labels=labels, targets=targets, ref=mask_loss_reference(logits, labels, targets))
