@@ -885,6 +885,54 @@ int detops_eval_oks(const float* dt_kpts, const float* gt_kpts, const float* gt_
                     detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Proposal recall (csrc/eval_proposals.hip; reference data/datasets/evaluation/coco/coco_eval.py, evaluate_box_proposals:
+ * the average recall of RPN proposals, `box_only`).  For every image, every proposal limit and every area range the
+ * reference runs a Python loop of min(P, G) rounds over the [P, G] IoU matrix; here all of them are one launch, and the
+ * matrix never exists in memory.  Unlike the COCO-style rules above this is no restatement from memory: the reference's
+ * function is plain torch, and tests/golden/box_proposals_reference.npz holds what it returned.
+ *
+ *   dt_boxes [D_total, 4] fp32 xyxy: the proposals of a batch, image after image; inside an image IN OBJECTNESS ORDER,
+ *     descending (the caller sorts).  gt_boxes [G_total, 4] fp32 xyxy.  dt_offset / gt_offset [N + 1] int32.
+ *   gt_valid [A, G_total] uint8: ground truth g counts in area range a (the caller compares the areas: fp32,
+ *     (area >= lo) & (area <= hi), both ends inclusive.  The reference compares an fp32 tensor when the json areas are
+ *     floats and an int64 tensor when they are all integers; the two differ only for areas above 2^24).
+ *   limits [L] int32: <= 0 for no limit, else the number of leading proposals of an image that take part.
+ *   overlaps [L, A, G_total] fp32, every element written exactly once.
+ *
+ * Per (image, limit l, range a):  P' = min(P, limits[l]) when limits[l] > 0, else P;  G' = the number of valid ground truths.
+ *   IoU[p, g] is boxlist_iou's fp32 expression, no operation contracted:
+ *     area = ((x2 - x1) + 1) * ((y2 - y1) + 1);   w, h = max((min(x2, X2) - max(x1, X1)) + 1, 0), likewise in y;
+ *     inter = w * h;   iou = inter / ((area_p + area_g) - inter), the correctly rounded fp32 quotient.
+ *   Then min(P', G') rounds: among the unused valid ground truths take the one whose largest IoU over the unused proposals
+ *   is largest (ties: the lowest ground-truth index); for it the proposal that attains that IoU (ties: the lowest proposal
+ *   index); write the IoU to the ground truth's slot and retire both.  This is the reference's overlaps.max(dim=0) /
+ *   max_overlaps.max(dim=0) with the first maximum taken, which is what the fixture's built ties show torch to do.
+ *   A valid ground truth no round reaches gets 0, a ground truth with gt_valid == 0 gets -1.
+ *   Outside the contract: boxes with x2 < x1 - 1 or y2 < y1 - 1, NaN coordinates, and two boxes of area 0 (their IoU is 0 / 0,
+ *   on which the reference's own assertion fails).  They may give any value; they never cause an access outside the arrays
+ *   (a NaN IoU is never selected).
+ *
+ * One workgroup per (image, limit, range) holds the image's boxes in LDS and, per ground truth, the best (IoU, proposal)
+ * among the unused proposals; a round is an argmax over those, and only the ground truths whose best was the retired
+ * proposal are scanned again.  No atomics: two runs give identical bits.
+ * max_dt / max_gt: the largest P' and the largest G of any image of the call, as the CALLER knows them on the host (they
+ *   size the LDS; nothing is read back from the device).  THE LARGEST SERVED ARE DETOPS_EVAL_PROPOSALS_MAX_DT AND
+ *   DETOPS_EVAL_PROPOSALS_MAX_GT: above either the entry point returns DETOPS_EUNSUPPORTED with nothing launched, and the
+ *   caller computes the call on the host.  An image larger than stated is cut to max_dt proposals, and its ground truths
+ *   from max_gt on are never matched (0 or -1); offsets that leave [0, D_total] / [0, G_total] make the image's workgroups
+ *   write nothing.
+ * DETOPS_EINVAL: N < 0, L < 1, A < 1, D_total < 0, G_total < 0, max_dt < 0, max_gt < 0, N * L * A >= 2^31; with N > 0 and
+ * G_total > 0 a null dt_offset, gt_offset, gt_boxes, gt_valid, limits or overlaps, or a null dt_boxes with D_total > 0.
+ * N == 0 or G_total == 0 is a no-op.  No workspace.
+ * ---------------------------------------------------------------------------------------- */
+#define DETOPS_EVAL_PROPOSALS_MAX_DT 2048
+#define DETOPS_EVAL_PROPOSALS_MAX_GT 1024
+int detops_eval_proposal_overlaps(const float* dt_boxes, const float* gt_boxes, const int32_t* dt_offset,
+                                  const int32_t* gt_offset, const unsigned char* gt_valid, const int32_t* limits, int N, int L,
+                                  int A, int64_t D_total, int64_t G_total, int max_dt, int max_gt, float* overlaps,
+                                  detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Batch image preparation (csrc/image_prep.hip; extension: the reference resizes every image on the CPU with
  * torchvision over Pillow, data/transforms/transforms.py, and copies the padded fp32 batch to the device).  One launch
  * takes the raw RGB uint8 HWC images of a batch to the zero-padded fp32 batch tensor: Resize, RandomHorizontalFlip,

@@ -1433,6 +1433,53 @@ def eval_oks(dt_kpts, gt_kpts, gt_boxes, gt_area, sigmas, dt_offset, gt_offset, 
     return oks, area
 
 
+EVAL_PROPOSALS_MAX_DT = _lib._abi.EVAL_PROPOSALS_MAX_DT      # DETOPS_EVAL_PROPOSALS_MAX_DT / _MAX_GT: the largest number of
+EVAL_PROPOSALS_MAX_GT = _lib._abi.EVAL_PROPOSALS_MAX_GT      # proposals taking part / ground truths of one image served
+
+
+def eval_proposal_overlaps(dt_boxes, gt_boxes, dt_offset, gt_offset, gt_valid, limits, max_dt=None, max_gt=None):
+    """The greedy matching behind the average recall of proposals, for every (limit, area range) of a batch in one launch
+    (include/detops.h: detops_eval_proposal_overlaps).  dt_boxes [D_total, 4] fp32 xyxy, image after image and in
+    objectness order (descending) inside an image; gt_boxes [G_total, 4]; dt_offset / gt_offset [N + 1] int32; gt_valid
+    [A, G_total] bool / uint8; limits: a sequence of L ints (<= 0 or None: no limit) -> float32 [L, A, G_total]: the IoU a
+    ground truth is matched with, 0 where no round reaches it, -1 where gt_valid is 0.
+    max_dt / max_gt: the largest number of proposals / ground truths of one image, where the caller knows them on the host
+    (None: read from the offsets).  Device tensors go to the kernel; CPU tensors, and images beyond
+    EVAL_PROPOSALS_MAX_DT proposals taking part or EVAL_PROPOSALS_MAX_GT ground truths, take the numpy form of the same
+    definition (_eval_cpu.eval_proposal_overlaps)."""
+    if dt_offset.dtype != torch.int32 or gt_offset.dtype != torch.int32 or not (dt_offset.numel() == gt_offset.numel() >= 1):
+        raise ValueError("eval_proposal_overlaps: expected dt_offset / gt_offset [N + 1] int32")
+    dt_offset, gt_offset = dt_offset.contiguous(), gt_offset.contiguous()
+    N = dt_offset.numel() - 1
+    dt_boxes, gt_boxes = (t.to(torch.float32).contiguous().reshape(-1, 4) for t in (dt_boxes, gt_boxes))
+    D_total, G_total = dt_boxes.shape[0], gt_boxes.shape[0]
+    limits = [0 if v is None else int(v) for v in limits]
+    if not limits or gt_valid.dim() != 2 or gt_valid.shape[0] < 1 or gt_valid.shape[1] != G_total:
+        raise ValueError("eval_proposal_overlaps: expected at least one limit and gt_valid [A >= 1, %d], got %d and %s"
+                         % (G_total, len(limits), tuple(gt_valid.shape)))
+    gt_valid = _u8("eval_proposal_overlaps", gt_valid)
+    L, A = len(limits), gt_valid.shape[0]
+    tensors = (dt_boxes, gt_boxes, dt_offset, gt_offset, gt_valid)
+    dev = gt_boxes.device
+    if max_dt is None or max_gt is None:
+        do, go = _np(dt_offset).astype(np.int64), _np(gt_offset).astype(np.int64)
+        max_dt = int(np.diff(do).max()) if N else 0
+        max_gt = int(np.diff(go).max()) if N else 0
+    part = max(min(int(max_dt), v) if v > 0 else int(max_dt) for v in limits)       # the largest P' of the call
+    if not any(on_device(t) for t in tensors) or part > EVAL_PROPOSALS_MAX_DT or int(max_gt) > EVAL_PROPOSALS_MAX_GT:
+        out = _eval_cpu.eval_proposal_overlaps(_np(dt_boxes), _np(gt_boxes), _np(dt_offset), _np(gt_offset), _np(gt_valid), limits)
+        return torch.from_numpy(out).to(dev)
+    _need_cuda("eval_proposal_overlaps", *tensors)
+    out = torch.empty((L, A, G_total), dtype=torch.float32, device=dev)
+    if N and G_total:
+        lim = torch.tensor(limits, dtype=torch.int32).to(dev)
+        with _on_device(out), _timed(("eval_proposal_overlaps[N=%d,D=%d,G=%d]", (N, D_total, G_total)), out):
+            check(lib.detops_eval_proposal_overlaps(ptr(dt_boxes), ptr(gt_boxes), ptr(dt_offset), ptr(gt_offset), ptr(gt_valid),
+                                                    ptr(lim), N, L, A, D_total, G_total, part, int(max_gt), ptr(out),
+                                                    stream_of(out)), "eval_proposal_overlaps")
+    return out
+
+
 def match_labels(matched, gt_labels=None, valid=None, dtype=torch.int64):
     """Matcher output [N,K] -> labels in one launch (extension; reference modeling/rpn/loss.py:70-88,
     roi_heads/box_head/loss.py:56-72): matched >= 0 -> gt_labels[n, matched] (1 when gt_labels is None), -1 -> 0,

@@ -265,3 +265,53 @@ def eval_oks(dt_kpts, gt_kpts, gt_boxes, gt_area, sigmas, dt_offset, gt_offset, 
     for k in range(K):
         s = np.where(counts[:, k], s + term[:, k], s)
     return s / np.where(k1 > 0, k1, K).astype(np.float64), dt_area
+
+
+# ------------------------------------------------------------------------------------------------ proposal recall
+def proposal_iou(dt, gt):
+    """boxlist_iou in fp32 numpy, one operation after the other (include/detops.h, "Proposal recall"): [P, 4], [G, 4] xyxy
+    -> [P, G] float32"""
+    dt, gt = np.asarray(dt, np.float32).reshape(-1, 4), np.asarray(gt, np.float32).reshape(-1, 4)
+    one, zero = np.float32(1), np.float32(0)
+    area_p = ((dt[:, 2] - dt[:, 0]) + one) * ((dt[:, 3] - dt[:, 1]) + one)
+    area_g = ((gt[:, 2] - gt[:, 0]) + one) * ((gt[:, 3] - gt[:, 1]) + one)
+    w = np.maximum((np.minimum(dt[:, None, 2], gt[None, :, 2]) - np.maximum(dt[:, None, 0], gt[None, :, 0])) + one, zero)
+    h = np.maximum((np.minimum(dt[:, None, 3], gt[None, :, 3]) - np.maximum(dt[:, None, 1], gt[None, :, 1])) + one, zero)
+    inter = w * h
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        return inter / ((area_p[:, None] + area_g[None, :]) - inter)
+
+
+def eval_proposal_overlaps(dt_boxes, gt_boxes, dt_offset, gt_offset, gt_valid, limits):
+    """include/detops.h, "Proposal recall": the proposals [D_total, 4] (objectness descending inside an image) and ground
+    truths [G_total, 4] of a batch, fp32 xyxy, dt_offset / gt_offset [N + 1], gt_valid [A, G_total], limits [L] (<= 0: no
+    limit) -> float32 [L, A, G_total]: the IoU every ground truth is matched with, 0 where no round reaches it, -1 outside
+    the area range.  The rounds are the reference's loop (evaluate_box_proposals), numpy's max / argmax in torch's place:
+    both take the first maximum."""
+    dt_boxes, gt_boxes = np.asarray(dt_boxes, np.float32).reshape(-1, 4), np.asarray(gt_boxes, np.float32).reshape(-1, 4)
+    dt_offset, gt_offset = np.asarray(dt_offset, np.int64).reshape(-1), np.asarray(gt_offset, np.int64).reshape(-1)
+    limits = np.asarray(limits, np.int64).reshape(-1)
+    G_total = gt_boxes.shape[0]
+    gt_valid = np.asarray(gt_valid).reshape(-1, G_total) != 0
+    L, A = limits.size, gt_valid.shape[0]
+    out = np.where(gt_valid, np.float32(0), np.float32(-1))[None].repeat(L, axis=0).astype(np.float32)
+    for n in range(dt_offset.size - 1):
+        d0, d1, g0, g1 = dt_offset[n], dt_offset[n + 1], gt_offset[n], gt_offset[n + 1]
+        if d1 <= d0 or g1 <= g0:
+            continue
+        iou = proposal_iou(dt_boxes[d0:d1], gt_boxes[g0:g1])
+        for li, limit in enumerate(limits):
+            rows = iou[:limit] if limit > 0 else iou
+            for a in range(A):
+                cols = np.nonzero(gt_valid[a, g0:g1])[0]
+                if cols.size == 0:
+                    continue
+                overlaps = rows[:, cols].copy()
+                for _ in range(min(overlaps.shape)):
+                    argmax_overlaps, max_overlaps = overlaps.argmax(axis=0), overlaps.max(axis=0)
+                    gt_ind = int(max_overlaps.argmax())
+                    box_ind = int(argmax_overlaps[gt_ind])
+                    out[li, a, g0 + cols[gt_ind]] = overlaps[box_ind, gt_ind]
+                    overlaps[box_ind, :] = -1
+                    overlaps[:, gt_ind] = -1
+    return out

@@ -5,8 +5,12 @@ Keypoints are scored under names of their own (keypoint_oks.py: KeypointOKSEvalu
 evaluate_keypoint_file; `inference(keypoint_oks=True)`; tools/evaluate_keypoints.py).  `evaluate`, `check_scope` and
 COCOStyleEvaluator still refuse the `keypoints` IoU type: routing the generic names to OKS is a later change.
 
-Not built, and raising NotImplementedError: `box_only` (the AR of RPN proposals), the `keypoints` IoU type through the
-generic entry points and the Cityscapes evaluator.
+The average recall of RPN proposals (`box_only`) has names of its own too (box_proposals.py: BoxProposalEvaluator,
+evaluate_box_proposals, do_box_proposal_evaluation; `inference(box_only=True)`); `evaluate`, `coco_evaluation` and
+`check_scope` still refuse `box_only`.
+
+Not built, and raising NotImplementedError: `box_only` and the `keypoints` IoU type through the generic entry points, and
+the Cityscapes evaluator.
 """
 import logging
 import os
@@ -14,6 +18,8 @@ from collections import OrderedDict
 
 import torch
 
+from .box_proposals import (BoxProposalEvaluator, do_box_proposal_evaluation, evaluate_box_proposals,  # noqa: F401
+                            finish_box_proposals)
 from .coco_style import STAT_NAMES, STAT_ROWS, COCOStyleEvaluator, _feed, _num_classes  # noqa: F401
 from .keypoint_oks import KeypointOKSEvaluator, evaluate_keypoint_file, load_keypoint_results  # noqa: F401
 from .voc import do_voc_evaluation, eval_detection_voc  # noqa: F401
@@ -45,7 +51,8 @@ def evaluate(dataset, predictions, output_folder, **kwargs):
 
 def check_scope(box_only, iou_types):
     if box_only:
-        raise NotImplementedError("box_only (the AR of RPN proposals) is not built")
+        raise NotImplementedError("box_only (the AR of RPN proposals) is not served by the generic entry points: it runs "
+                                  "through inference(box_only=True), BoxProposalEvaluator and evaluate_box_proposals")
     if "keypoints" in iou_types:
         raise NotImplementedError("the keypoints IoU type is not served by the generic entry points: OKS runs through "
                                   "inference(keypoint_oks=True), KeypointOKSEvaluator and tools/evaluate_keypoints.py")

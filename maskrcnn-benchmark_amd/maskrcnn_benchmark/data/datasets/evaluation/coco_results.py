@@ -23,7 +23,7 @@ strings"); `evaluate_result_files` scores the files against a dataset's ground t
 keypoint_oks.evaluate_keypoint_file (tools/evaluate_keypoints.py); `load_results` and `evaluate_result_files` still refuse
 "keypoints".
 
-Not built: `box_only` proposals."""
+No file is written for `box_only` proposals: they are scored in the loop (box_proposals.py)."""
 import json
 import os
 

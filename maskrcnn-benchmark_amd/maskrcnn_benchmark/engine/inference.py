@@ -3,7 +3,8 @@ model(images.to(device)) -> targets to the device -> evaluator.update; the predi
 where they were made and only the match records are kept (data/datasets/evaluation/coco_style.py).  With an output folder the
 detections themselves are written as COCO result files (data/datasets/evaluation/coco_results.py: bbox.json, segm.json,
 keypoints.json), batch by batch next to the evaluator; `evaluate=False` writes them and matches nothing.  Keypoints are
-scored on request (`keypoint_oks=True`: data/datasets/evaluation/keypoint_oks.py).  Single process only.
+scored on request (`keypoint_oks=True`: data/datasets/evaluation/keypoint_oks.py).  The proposals of an RPN-only model
+are scored by their average recall (`box_only=True`: data/datasets/evaluation/box_proposals.py).  Single process only.
 Datasets that are not COCO-shaped keep the reference's flow: the predictions are collected and handed to `evaluate`."""
 import logging
 import os
@@ -11,7 +12,8 @@ import time
 
 import torch
 
-from maskrcnn_benchmark.data.datasets.evaluation import COCOStyleEvaluator, check_scope, dataset_style, finish_coco
+from maskrcnn_benchmark.data.datasets.evaluation import (BoxProposalEvaluator, COCOStyleEvaluator, check_scope, dataset_style,
+                                                         finish_box_proposals, finish_coco)
 from maskrcnn_benchmark.data.datasets.evaluation import evaluate as evaluate_predictions
 from maskrcnn_benchmark.data.datasets.evaluation.coco_results import COCOResultsWriter
 from maskrcnn_benchmark.data.datasets.evaluation.coco_style import _num_classes
@@ -47,7 +49,12 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     annotations.  -> {iou type: path of its file}.
     keypoint_oks=True (COCO-shaped datasets, a model with a keypoint head, not under box augmentation): the loop also feeds a
     KeypointOKSEvaluator next to the evaluator of `iou_types`, the writer also writes keypoints.json, and the returned
-    COCOResults has a `keypoints` row.  "keypoints" in `iou_types` is still refused: OKS has names of its own."""
+    COCOResults has a `keypoints` row.  "keypoints" in `iou_types` is still refused: OKS has names of its own.
+    box_only=True (an RPN-only model, MODEL.RPN_ONLY: its output is the proposals with their `objectness`): on a COCO-shaped
+    dataset the loop feeds a BoxProposalEvaluator instead of the evaluator of `iou_types`, and the returned COCOResults has the
+    one row `box_proposal` (AR@100 ... ARl@1000), saved as box_proposals.pth / box_proposals.txt; no result files are written
+    for proposals.  Not together with keypoint_oks, evaluate=False or box augmentation.  ValueError: the model's output has
+    no `objectness`, i.e. the model is not RPN-only."""
     if not evaluate and not output_folder:
         raise ValueError("inference(evaluate=False) writes result files only: it needs output_folder=")
     if get_world_size() > 1:
@@ -84,8 +91,12 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     if not evaluate and (not streaming or box_only):
         raise NotImplementedError("inference(evaluate=False): result files are written for COCO-shaped datasets and detections "
                                   "only (not box_only proposals)")
-    if streaming and evaluate:
-        check_scope(box_only, iou_types)
+    if box_only and bbox_aug:
+        raise NotImplementedError("inference(box_only=True): proposals are not scored under box augmentation")
+    if streaming and evaluate and box_only:
+        evaluators = [BoxProposalEvaluator()]
+    elif streaming and evaluate:
+        check_scope(False, iou_types)
         evaluators = [COCOStyleEvaluator(iou_types, _num_classes(dataset, 81))]
         if keypoint_oks:
             evaluators.append(KeypointOKSEvaluator(_num_classes(dataset, 2)))
@@ -103,6 +114,9 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
                 # a model whose config could not be found (a wrapper without `.module`) and that was built with BBOX_AUG
                 raise ValueError("the model returned boxes without `labels`: it was built with TEST.BBOX_AUG.ENABLED and is "
                                  "evaluated with inference(bbox_aug=True, cfg=...)")
+            if box_only and any(len(o) and not o.has_field("objectness") for o in output):
+                raise ValueError("inference(box_only=True): the model returned boxes without `objectness`: it is not RPN-only "
+                                 "(MODEL.RPN_ONLY); detections are evaluated with box_only=False")
             if device.type != "cpu":
                 torch.cuda.synchronize()
             model_time += time.time() - t0
@@ -130,6 +144,8 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     if streaming:
         logger.info("Matched {} detections against {} ground truths of {} images".format(
             evaluators[0].num_detections, evaluators[0].num_groundtruths, evaluators[0].num_images))
+        if box_only:
+            return finish_box_proposals(evaluators[0], output_folder, expected_results, expected_results_sigma_tol)
         return finish_coco(evaluators, output_folder, expected_results, expected_results_sigma_tol)
     predictions = [predictions[i] for i in sorted(predictions)]
     if output_folder:

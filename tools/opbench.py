@@ -1073,6 +1073,78 @@ def bench_keypoint_oks(C, iters):
     return out
 
 
+def bench_proposal_recall(C, iters):
+    """proposal recall (csrc/eval_proposals.hip): 2 images, 1000 proposals and 20 ground truths each, the 2 limits x 4 area
+    ranges of the `box_proposal` table (16 workgroups, 20 rounds each at most).  Rows: the entry point alone on prebuilt
+    device arrays; _C.eval_proposal_overlaps through the wrapper (its dtype / contiguity checks, the copy of the limits and
+    one allocation included); the reference's loop (evaluate_box_proposals) as torch operations on the same device tensors,
+    once per (image, limit, area range).  bytes = the boxes, offsets and flags read once + the overlaps written."""
+    from maskrcnn_benchmark import _eval_cpu, _lib
+    N, P, G, limits = 2, 1000, 20, (100, 1000)
+    ranges = ((0, 1e10), (0, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e10))
+    rng = np.random.RandomState(5)
+    x1, y1 = rng.uniform(0, 1100, N * G), rng.uniform(0, 600, N * G)
+    side = np.exp(rng.uniform(np.log(12), np.log(400), N * G))
+    gt = np.stack([x1, y1, x1 + side, y1 + side * rng.uniform(0.5, 2, N * G)], 1).astype(np.float32)
+    x1, y1 = rng.uniform(0, 1200, N * P), rng.uniform(0, 700, N * P)
+    dt = np.stack([x1, y1, x1 + rng.uniform(8, 400, N * P), y1 + rng.uniform(8, 400, N * P)], 1).astype(np.float32)
+    near = np.repeat(gt.reshape(N, G, 4), 10, axis=1).reshape(N, G * 10, 4) + rng.uniform(-12, 12, (N, G * 10, 4))
+    dt.reshape(N, P, 4)[:, :G * 10] = near                      # ten jittered copies of every ground truth among the proposals
+    dt = dt.reshape(N, P, 4)[:, rng.permutation(P)].reshape(-1, 4).copy()
+    dt[:, 2:] = np.maximum(dt[:, 2:], dt[:, :2] + 1)
+    area = ((gt[:, 2] - gt[:, 0]) + 1) * ((gt[:, 3] - gt[:, 1]) + 1)
+    valid = np.stack([(area >= lo) & (area <= hi) for lo, hi in ranges]).astype(np.uint8)
+    dto, gto = (np.arange(N + 1) * P).astype(np.int32), (np.arange(N + 1) * G).astype(np.int32)
+    lim = np.array(limits, np.int32)
+    dt_d, gt_d, dto_d, gto_d, valid_d, lim_d = (_t(a) for a in (dt, gt, dto, gto, valid, lim))
+    L, A = len(limits), len(ranges)
+    alg = (dt.size + gt.size) * 4 + (dto.size + gto.size + lim.size) * 4 + valid.size + L * A * N * G * 4
+    out = torch.empty((L, A, N * G), dtype=torch.float32, device="cuda")
+    raw = lambda: _lib.check(_lib.lib.detops_eval_proposal_overlaps(  # noqa: E731
+        dt_d.data_ptr(), gt_d.data_ptr(), dto_d.data_ptr(), gto_d.data_ptr(), valid_d.data_ptr(), lim_d.data_ptr(), N, L, A, N * P,
+        N * G, P, G, out.data_ptr(), _lib.stream_of(out)), "eval_proposal_overlaps")
+    name = "2 x (1000 x 20), 2 limits x 4 ranges"
+    res = [_entry("detops_eval_proposal_overlaps entry point, " + name, dev_time_us(raw, iters), alg)]
+    wrapped = lambda: C.eval_proposal_overlaps(dt_d, gt_d, dto_d, gto_d, valid_d, limits, max_dt=P, max_gt=G)  # noqa: E731
+    res.append(_entry("_C.eval_proposal_overlaps through the wrapper, same batch", dev_time_us(wrapped, iters), alg))
+    ref = _eval_cpu.eval_proposal_overlaps(dt, gt, dto, gto, valid, lim)
+    res[-1].update({"equal_to_numpy": bool(np.array_equal(wrapped().cpu().numpy(), ref)),
+                    "matched": int((ref > 0).sum()), "slots": int((ref >= 0).sum())})
+
+    def torch_loop():
+        result = torch.full((L, A, N * G), -1.0, device="cuda")
+        for n in range(N):
+            boxes, gts = dt_d[n * P:(n + 1) * P], gt_d[n * G:(n + 1) * G]
+            for li, limit in enumerate(limits):
+                for a in range(A):
+                    keep = valid_d[a, n * G:(n + 1) * G] != 0
+                    g = gts[keep]
+                    if len(g) == 0:
+                        continue
+                    p = boxes[:limit]
+                    area_p = (p[:, 2] - p[:, 0] + 1) * (p[:, 3] - p[:, 1] + 1)
+                    area_g = (g[:, 2] - g[:, 0] + 1) * (g[:, 3] - g[:, 1] + 1)
+                    wh = (torch.min(p[:, None, 2:], g[:, 2:]) - torch.max(p[:, None, :2], g[:, :2]) + 1).clamp(min=0)
+                    inter = wh[:, :, 0] * wh[:, :, 1]
+                    overlaps = inter / (area_p[:, None] + area_g - inter)
+                    found = torch.zeros(len(g), device="cuda")
+                    slot = torch.nonzero(keep).reshape(-1)
+                    for j in range(min(len(p), len(g))):
+                        max_overlaps, argmax_overlaps = overlaps.max(dim=0)
+                        gt_ovr, gt_ind = max_overlaps.max(dim=0)
+                        box_ind = argmax_overlaps[gt_ind]
+                        found[gt_ind] = overlaps[box_ind, gt_ind]
+                        overlaps[box_ind, :] = -1
+                        overlaps[:, gt_ind] = -1
+                    result[li, a, n * G + slot] = found
+        return result
+
+    us = dev_time_us(torch_loop, max(iters // 10, 3), warmup=2)
+    res.append(_entry("torch: the reference's loop on the same device tensors", us, alg,
+                      {"equal_to_numpy": bool(np.array_equal(torch_loop().cpu().numpy(), ref))}))
+    return res
+
+
 def copy_ceiling(iters):
     a = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
     b = torch.empty_like(a)
@@ -1140,6 +1212,8 @@ def main():
         res += bench_evaluation(C, args.iters)
     if not only or "keypoint_oks" in only:
         res += bench_keypoint_oks(C, args.iters)
+    if not only or "proposal_recall" in only:
+        res += bench_proposal_recall(C, args.iters)
     if not only or "coco_results" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_coco_results(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
