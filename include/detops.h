@@ -974,6 +974,66 @@ int detops_image_batch_u8(const uint8_t* raw, int64_t raw_bytes, const int64_t* 
                           float* out, detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Colour jitter of the raw images of a batch (csrc/color_jitter.hip; the reference's data/transforms/transforms.py
+ * ColorJitter hands the PIL image to torchvision's, which is a thin layer over Pillow: ImageEnhance.Brightness / Contrast /
+ * Color, i.e. Image.blend against a degenerate image, and an add on the H plane of convert("HSV")).  IN PLACE on the
+ * device copy of the raw bytes detops_image_batch_u8 reads afterwards.
+ *
+ * An image is h x w RGB bytes.  It has up to four steps, each operation at most once, in a per-image order.  Everything
+ * is evaluated exactly as written, nothing contracted into an FMA.
+ *   blend(d, x, a), per byte; a = the factor rounded to fp32, d the "degenerate" byte, x the image byte:
+ *     t = float(d) + a * float(x - d)          (the INTEGER difference is converted; one fp32 multiply, one fp32 add)
+ *     0 <= a <= 1:  uint8(trunc(t));   otherwise 0 for t <= 0, 255 for t >= 255, else uint8(trunc(t))
+ *   L(r, g, b) = (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16                                       (convert("L"))
+ *   brightness(f):  blend(0, x, f)
+ *   saturation(f):  blend(L(pixel), x, f) on each channel
+ *   contrast(f):    blend(m, x, f);  m = int(S / (h * w) + 0.5) in fp64, S the integer sum of L over the whole image AS IT
+ *                   IS WHEN THE STEP IS REACHED, i.e. after the steps in front of it
+ *   hue(k), k in 0 .. 255:  RGB -> HSV,  H = (H + k) & 255,  HSV -> RGB
+ *   RGB -> HSV:  maxc, minc = the largest and smallest byte;  V = maxc;  minc == maxc: H = S = 0.  Otherwise in fp32
+ *     cr = float(maxc - minc);  s = cr / float(maxc);  rc = float(maxc - r) / cr, gc and bc likewise;
+ *     r == maxc: h = bc - gc (fp32);  else g == maxc: h = float(2.0 + rc - bc);  else h = float(4.0 + gc - rc)   (the last
+ *     two in fp64, left to right, rounded to fp32 once);  h = float(fmod(double(h) / 6.0 + 1.0, 1.0));
+ *     H = clip8(int(double(h) * 255.0));  S = clip8(int(double(s) * 255.0))                          (int: the C cast)
+ *   HSV -> RGB:  S == 0: (V, V, V).  Otherwise h6 = double(H) * 6.0 / 255.0;  i = floor(h6);  f = float(h6 - float(i));
+ *     fs = float(double(S) / 255.0);  in fp64, round = half away from zero, then clip8:
+ *     p = round(V * (1.0 - fs));  q = round(V * (1.0 - fs * f));  t = round(V * (1.0 - fs * (1.0 - f)))
+ *     (R, G, B) by i % 6:  0 (V,t,p)  1 (q,V,p)  2 (p,V,t)  3 (p,q,V)  4 (t,p,V)  5 (V,p,q)       (H = 255: i = 6, case 0)
+ * WHAT WAS CHECKED: this arithmetic equals Pillow 12.2.0 (x86-64) on all 2^24 RGB colours for convert("L"), the three
+ * enhancers at seven factors and RGB -> HSV, and on all 2^24 HSV triples for HSV -> RGB, with no differing byte
+ * (tests/golden/make_golden_color_jitter.py, profiles/color_jitter_exhaustive.txt).  Pillow's C code is compiled without
+ * FMA contraction on x86-64; a Pillow build for another host may contract the blend and differ in the last bit.
+ * WHAT WAS NOT: the parameters (data/transforms/transforms.py RawColorJitter).  A number v >= 0 for brightness, contrast
+ * or saturation means a factor uniform in [max(0, 1 - v), 1 + v], hue 0 <= v <= 0.5 uniform in [-v, v], a (lo, hi) pair is
+ * taken as given; a range that is the identity disables the operation, which then makes no draw; k = int(f * 255) mod 256
+ * (fp64 product, truncated toward zero).  Draws from Python's `random`: one uniform per enabled operation in the order
+ * brightness, contrast, saturation, hue, then one shuffle of the enabled operations.  This draw order is THIS LIBRARY'S
+ * DEFINITION, written as torchvision's ColorJitter.get_params is recalled; it was not checked against torchvision.
+ *
+ *   raw, offsets, geom, geom_host   as detops_image_batch_u8 (h and w are read from the records; raw is WRITTEN)
+ *   jitter     int32 [N, DETOPS_COLOR_JITTER_FIELDS] per image: four step codes in the order they run (0 none,
+ *              1 brightness, 2 contrast, 3 saturation, 4 hue; the list ends at the first 0 and only 0 may follow it), then
+ *              the four parameters at the same positions: the fp32 bits of the factor, or k.  On the device, and the same
+ *              records on the host as jitter_host (validated before anything is launched).
+ *   workspace  N * 8 bytes on the device (the images' sums of L, 64-bit: 255 h w passes 2^32 from 16.8 M pixels); only
+ *              used, and only required, when some image has a contrast step.
+ * At most two kernel launches (and one 8 N byte memset in front of the first): a sum pass when some image has a contrast
+ * step (the steps in front of contrast are applied on the fly, nothing is written to the images), then the apply pass.
+ * Every byte of every image with at least one step is written exactly once; no other byte of `raw` is written.
+ * DETOPS_EINVAL with nothing launched: N < 0, raw_bytes < 0, a null pointer (workspace: only with a contrast step), a
+ * record with h or w < 1, an unknown step code, a code after the end of the list, an operation given twice, k outside
+ * 0 .. 255, a non-finite factor.  DETOPS_EWORKSPACE: a workspace under N * 8 bytes with a contrast step.  N == 0 or no
+ * image with a step is a no-op with no launch.  The kernel bounds every access by the image's own byte range and by
+ * raw_bytes: a record on the device that differs from its host copy cannot make it leave the buffer (an image it cannot
+ * serve is skipped).
+ * ---------------------------------------------------------------------------------------- */
+#define DETOPS_COLOR_JITTER_FIELDS 8
+#define DETOPS_COLOR_JITTER_MAX_STEPS 4
+int detops_color_jitter_u8(uint8_t* raw, int64_t raw_bytes, const int64_t* offsets, const int32_t* geom,
+                           const int32_t* geom_host, const int32_t* jitter, const int32_t* jitter_host, int N,
+                           void* workspace, size_t workspace_bytes, detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Merge of test-time box augmentation (csrc/bbox_aug.hip; the reference's engine/bbox_aug.py maps every pass's BoxList
  * back with BoxList.transpose / resize, concatenates them per image and runs filter_results' per-class loop).  The passes
  * of a batch hand in their unfiltered per-class boxes; the merge maps them to the frame of the image's first pass and

@@ -1089,6 +1089,48 @@ def image_batch(raw, offsets, geom, table, bgr, Hp, Wp, channels_last=False, geo
     return out
 
 
+def color_jitter(raw, offsets, geom, jitter, geom_host=None, jitter_host=None):
+    """Colour jitter of the raw images of a batch, IN PLACE on `raw` (extension; include/detops.h: detops_color_jitter_u8):
+    raw, offsets, geom as image_batch; jitter [N, 8] int32 per image: four step codes in the order they run (0 none,
+    1 brightness, 2 contrast, 3 saturation, 4 hue) and their four parameters (the fp32 bits of the factor, or hue's byte
+    shift k).  Pillow's ImageEnhance and HSV arithmetic, byte for byte.  geom_host, jitter_host: the CPU copies when the
+    caller has them (else they are read back).  Returns raw.  CPU tensors take the numpy implementation of the same
+    definition (_color_jitter_cpu.py)."""
+    from . import _color_jitter_cpu, _image_prep_cpu
+
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 \
+            or geom.dtype != torch.int32 or geom.dim() != 2 or geom.shape[1] != _image_prep_cpu.GEOM_FIELDS \
+            or jitter.dtype != torch.int32 or jitter.dim() != 2 or jitter.shape[1] != _color_jitter_cpu.FIELDS \
+            or not offsets.numel() == geom.shape[0] == jitter.shape[0]:
+        raise ValueError("color_jitter: expected raw [bytes] uint8, offsets [N] int64, geom [N, 5] int32, jitter [N, 8] int32")
+    tensors = (raw, offsets, geom, jitter)
+    N = geom.shape[0]
+    if not any(on_device(t) for t in tensors):
+        if not raw.is_contiguous():
+            raise ValueError("color_jitter: raw is changed in place and must be contiguous")
+        _color_jitter_cpu.color_jitter(raw.numpy(), offsets.numpy(), geom.numpy(), jitter.numpy())
+        return raw
+    _need_cuda("color_jitter", *tensors)
+    if not raw.is_contiguous():
+        raise ValueError("color_jitter: raw is changed in place and must be contiguous")
+    offsets, geom, jitter = (t.contiguous() for t in (offsets, geom, jitter))
+    geom_host = (geom.cpu() if geom_host is None else geom_host.to(torch.int32)).contiguous()
+    jitter_host = (jitter.cpu() if jitter_host is None else jitter_host.to(torch.int32)).contiguous()
+    if geom_host.is_cuda or tuple(geom_host.shape) != tuple(geom.shape) or jitter_host.is_cuda \
+            or tuple(jitter_host.shape) != tuple(jitter.shape):
+        raise ValueError("color_jitter: geom_host and jitter_host are the CPU copies of geom and jitter")
+    if N == 0:
+        return raw
+    with _on_device(raw), _timed(("color_jitter[N=%d,%d bytes]", (N, raw.numel())), raw):
+        ws = torch.empty(N, dtype=torch.int64, device=raw.device)
+        rc = lib.detops_color_jitter_u8(ptr(raw), raw.numel(), ptr(offsets), ptr(geom), ptr(geom_host), ptr(jitter),
+                                        ptr(jitter_host), N, ptr(ws), ws.numel() * 8, stream_of(raw))
+    if rc == _EINVAL:                                  # the entry point validated the records (nothing was launched):
+        _color_jitter_cpu.check_records(jitter_host.numpy())       # its refusal with the reason, off the per-batch path
+    check(rc, "color_jitter")
+    return raw
+
+
 # ------------------------------------------------------------------------------------------ test-time box augmentation
 def bbox_aug_merge(boxes, scores, row_offset, group_geom, group_ratio, N, T, score_thresh):
     """The merge of test-time box augmentation (extension; include/detops.h: detops_bbox_aug_merge_count / _write): boxes

@@ -90,6 +90,7 @@ SIGNATURES = {
     "detops_polygon_mask_targets": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
     "detops_polygons_to_masks": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P, _P]),
     "detops_image_batch_u8": (c_int, [_P, ctypes.c_int64, _P, _P, _P, c_int, _P] + [c_int] * 4 + [_P, _P]),
+    "detops_color_jitter_u8": (c_int, [_P, ctypes.c_int64] + [_P] * 5 + [c_int, _P, c_size_t, _P]),
     "detops_bbox_aug_merge_workspace_bytes": (c_size_t, [c_int] * 3),
     "detops_bbox_aug_merge_count": (c_int, [_P, _P, _P] + [c_int] * 4 + [c_float, _P, _P, _P, c_size_t, _P]),
     "detops_bbox_aug_merge_write": (c_int, [_P] * 6 + [c_int] * 4 + [c_float, _P, ctypes.c_int64, _P, _P, _P, c_size_t, _P]),

@@ -15,7 +15,7 @@ from maskrcnn_benchmark.utils.comm import get_world_size
 
 from . import collate_batch, samplers, synthetic
 from . import datasets as D
-from .transforms import build_transforms
+from .transforms import build_transforms, jitter_enabled
 
 
 def _is_synthetic(names):
@@ -89,8 +89,10 @@ def make_batch_data_sampler(dataset, sampler, aspect_grouping, images_per_batch,
 
 def deferred_prep(cfg, is_train):
     """are the pixels of this loader's batches deferred (ToRaw transforms, RawBatchCollator)?  The input path's switch
-    (collate_batch.device_prep), and always under test-time box augmentation: every pass is prepared from the raw bytes."""
-    return collate_batch.device_prep(cfg) or (not is_train and cfg.TEST.BBOX_AUG.ENABLED)
+    (collate_batch.device_prep), and always under test-time box augmentation: every pass is prepared from the raw bytes;
+    and always for a training loader with non-zero colour jitter, which only the deferred path serves (on a GPU and on the
+    CPU alike)."""
+    return collate_batch.device_prep(cfg) or (not is_train and cfg.TEST.BBOX_AUG.ENABLED) or jitter_enabled(cfg, is_train)
 
 
 def make_collator(cfg, is_train=True):

@@ -1,3 +1,3 @@
-from .build import build_transforms  # noqa: F401
-from .transforms import (ColorJitter, Compose, Normalize, RandomHorizontalFlip, RandomVerticalFlip, RawImage, Resize,  # noqa: F401
-                         ToRaw, ToTensor, normalisation_table)
+from .build import build_transforms, jitter_enabled  # noqa: F401
+from .transforms import (ColorJitter, Compose, Normalize, RandomHorizontalFlip, RandomVerticalFlip, RawColorJitter,  # noqa: F401
+                         RawImage, Resize, ToRaw, ToTensor, normalisation_table)

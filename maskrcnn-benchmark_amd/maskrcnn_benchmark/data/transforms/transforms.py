@@ -16,12 +16,14 @@ FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM = 0, 1      # BoxList.transpose / PIL.Image.tra
 
 class RawImage(object):
     """An image whose resize and flips are deferred: data [h, w, 3] uint8 (RGB), size (ow, oh) = what the PIL image's
-    `.size` would be by now, flip bits (1 horizontal, 2 vertical)."""
+    `.size` would be by now, flip bits (1 horizontal, 2 vertical), jitter = the colour steps that run on the source bytes
+    first, in order: (code, parameter) pairs (RawColorJitter), empty for none."""
 
-    def __init__(self, data, size=None, flip=0):
+    def __init__(self, data, size=None, flip=0, jitter=()):
         self.data = data
         self.size = (data.shape[1], data.shape[0]) if size is None else size
         self.flip = flip
+        self.jitter = tuple(jitter)
 
 
 class Compose(object):
@@ -70,7 +72,7 @@ class Resize(object):
     def __call__(self, image, target=None):
         oh, ow = self.get_size(image.size)
         if isinstance(image, RawImage):
-            image = RawImage(image.data, (ow, oh), image.flip)
+            image = RawImage(image.data, (ow, oh), image.flip, image.jitter)
         else:
             from PIL import Image
 
@@ -89,7 +91,7 @@ class _RandomFlip(object):
     def __call__(self, image, target):
         if random.random() < self.prob:
             if isinstance(image, RawImage):
-                image = RawImage(image.data, image.size, image.flip ^ self.bit)
+                image = RawImage(image.data, image.size, image.flip ^ self.bit, image.jitter)
             else:
                 image = image.transpose(self.method)       # PIL's FLIP_LEFT_RIGHT = 0, FLIP_TOP_BOTTOM = 1
             target = target.transpose(self.method)
@@ -111,10 +113,63 @@ class ColorJitter(object):
     def __init__(self, brightness=None, contrast=None, saturation=None, hue=None):
         if any(v not in (None, 0, 0.0) for v in (brightness, contrast, saturation, hue)):
             raise NotImplementedError("ColorJitter with non-zero BRIGHTNESS / CONTRAST / SATURATION / HUE needs torchvision's "
-                                      "definition, which is not built")
+                                      "definition, which is not built for the host pipeline (the deferred input path serves it: "
+                                      "RawColorJitter, build_transforms(cfg, is_train, device_prep=True))")
 
     def __call__(self, image, target):
         return image, target
+
+
+class RawColorJitter(object):
+    """ColorJitter of the deferred pipeline: draws the parameters and leaves the steps on the RawImage; the pixels are
+    jittered where the batch lands (include/detops.h: detops_color_jitter_u8, Pillow's arithmetic byte for byte).
+    torchvision's rules: a number v >= 0 for brightness / contrast / saturation is a factor uniform in [max(0, 1 - v),
+    1 + v], hue 0 <= v <= 0.5 is uniform in [-v, v], a (lo, hi) pair is taken as given; a range that is the identity
+    disables the operation, which then makes no draw.  Draws from `random`: one uniform per enabled operation in the order
+    brightness, contrast, saturation, hue, then one shuffle of the enabled operations.  That order is this library's
+    definition (torchvision's get_params as recalled; not checked against torchvision)."""
+    BRIGHTNESS, CONTRAST, SATURATION, HUE = 1, 2, 3, 4           # the step codes of the jitter record
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0):
+        self.brightness = self._range(brightness, "brightness")
+        self.contrast = self._range(contrast, "contrast")
+        self.saturation = self._range(saturation, "saturation")
+        self.hue = self._range(hue, "hue", center=0.0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+
+    @staticmethod
+    def _range(value, name, center=1.0, bound=(0.0, float("inf")), clip_first_on_zero=True):
+        if value is None:
+            return None
+        if isinstance(value, (int, float)):
+            if value < 0:
+                raise ValueError("%s must be non-negative, got %r" % (name, value))
+            lo, hi = center - float(value), center + float(value)
+            if clip_first_on_zero:
+                lo = max(lo, 0.0)
+        elif isinstance(value, (tuple, list)) and len(value) == 2:
+            lo, hi = float(value[0]), float(value[1])
+        else:
+            raise TypeError("%s is a number or a (lo, hi) pair, got %r" % (name, value))
+        if not bound[0] <= lo <= hi <= bound[1]:
+            raise ValueError("%s values must lie in %r, got %r" % (name, bound, value))
+        return None if lo == hi == center else (lo, hi)
+
+    @staticmethod
+    def hue_shift(factor):
+        """the byte added to the H plane: int(f * 255) mod 256 (the uint8 add wraps), fp64, truncated toward zero"""
+        return int(factor * 255) % 256
+
+    def __call__(self, image, target=None):
+        steps = []
+        for code, span in ((self.BRIGHTNESS, self.brightness), (self.CONTRAST, self.contrast),
+                           (self.SATURATION, self.saturation), (self.HUE, self.hue)):
+            if span is not None:
+                f = random.uniform(span[0], span[1])
+                steps.append((code, self.hue_shift(f) if code == self.HUE else f))
+        if steps:
+            random.shuffle(steps)
+        image = RawImage(image.data, image.size, image.flip, steps)
+        return image if target is None else (image, target)
 
 
 class ToTensor(object):

@@ -700,6 +700,73 @@ def bench_input_prep(C, iters, copy_gbs=None):
     return out
 
 
+def bench_color_jitter(C, iters, copy_gbs=None):
+    """colour jitter of one training batch (csrc/color_jitter.hip): two 480 x 640 RGB uint8 images on a device-resident
+    buffer, all four steps each, hue not last and contrast in the middle, so both launches run (the sum pass applies the
+    step in front of contrast on the fly).  The operator works in place and jittered bytes are not the workload (repeated
+    jitter drives an image to grey, which skips the hue path), so EVERY call starts from a pristine device copy of the
+    buffer, restored outside the timed span.
+    device rows: a HIP event pair per call; in front of the first event the stream is given ~0.3 ms of other work
+    (torch.cuda._sleep), so the memset and both launches are queued before the device reaches them and the span holds
+    device time, not the host's enqueue rate.  median and first call; bytes = the images read by the sum pass + read and
+    written by the apply pass; frac_of_copy_peak = those bytes over the median, against the copy row of the same run.
+    host row: the host clock around the Python wrapper call alone (no synchronise): what a call costs the host to enqueue.
+    The wrapper is host-bound when the host row exceeds the device row."""
+    from maskrcnn_benchmark import _color_jitter_cpu as J
+    from maskrcnn_benchmark._lib import lib, ptr, stream_of
+    from maskrcnn_benchmark.data import transforms as T
+    from maskrcnn_benchmark.data.collate_batch import RawImageBatch
+    rng = np.random.RandomState(3)
+    yy, xx = np.mgrid[0:480, 0:640]
+    srcs = [np.clip(np.stack([xx * 0.4, yy * 0.5, 128 + 100 * np.sin(0.05 * xx + 0.03 * yy + i)], 2) + rng.normal(0, 20, (480, 640, 3)),
+                    0, 255).astype(np.uint8) for i in range(2)]
+    steps = [[(J.SATURATION, 1.2), (J.CONTRAST, 0.9), (J.HUE, 13), (J.BRIGHTNESS, 1.1)],
+             [(J.HUE, 243), (J.CONTRAST, 1.1), (J.BRIGHTNESS, 0.9), (J.SATURATION, 0.8)]]
+    table = T.normalisation_table([102.9801, 115.9465, 122.7717], [1.0, 1.0, 1.0], True)
+    batch = RawImageBatch.pack([T.RawImage(s, (1066, 800), 0, st) for s, st in zip(srcs, steps)], table, True, 32)
+    pristine = batch.buffer.cuda()
+    buf = pristine.clone()
+    off, geom = buf[:16].view(torch.int64), buf[16:56].view(torch.int32).view(2, 5)
+    jit = buf[buf.numel() - 64:].view(torch.int32).view(2, 8)
+    ws = torch.empty(2, dtype=torch.int64, device="cuda")
+    grey = int(sum(((s[..., 0] == s[..., 1]) & (s[..., 1] == s[..., 2])).sum() for s in srcs))   # pixels that skip the hue path
+
+    def wrapper():
+        C.color_jitter(buf, off, geom, jit, geom_host=batch.geom, jitter_host=batch.jitter)
+
+    def entry():
+        rc = lib.detops_color_jitter_u8(ptr(buf), buf.numel(), ptr(off), ptr(geom), ptr(batch.geom), ptr(jit), ptr(batch.jitter), 2,
+                                        ptr(ws), 16, stream_of(buf))
+        assert rc == 0, rc
+
+    def device_us(fn, n):
+        spans, host = [], []
+        for _ in range(n + 3):
+            buf.copy_(pristine)
+            torch.cuda._sleep(600000)                      # the host runs ahead of the device
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            t0 = time.perf_counter()
+            fn()
+            host.append((time.perf_counter() - t0) * 1e6)
+            b.record()
+            torch.cuda.synchronize()
+            spans.append(a.elapsed_time(b) * 1000.0)
+        spans, host = spans[3:], host[3:]                  # three warm-up calls
+        return float(np.median(spans)), spans[0], float(np.median(host))
+
+    moved = 3 * 2 * 480 * 640 * 3
+    out = []
+    for name, fn in (("entry point", entry), ("wrapper", wrapper)):
+        med, first, host = device_us(fn, iters)
+        extra = {"launches": 2, "first_us": round(first, 2), "grey_source_pixels": grey}
+        if copy_gbs:
+            extra["frac_of_copy_peak"] = round(moved / med / 1e3 / copy_gbs, 4)
+        out.append(_entry("color_jitter 2 x 480x640, 4 steps each, device time, %s" % name, med, moved, extra))
+        out.append(_entry("color_jitter host time to enqueue one call, %s" % name, host, moved))
+    return out
+
+
 def bench_bbox_aug(C, iters, copy_gbs=None):
     """the merge of test-time box augmentation (csrc/bbox_aug.hip): N = 2 images, T = 6 passes, 1000 rows per group, 81
     classes, about 1 % of the (row, class) pairs above the score threshold.
@@ -1222,6 +1289,9 @@ def main():
     if not only or "input_prep" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_input_prep(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
+    if not only or "color_jitter" in only:
+        copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
+        res += bench_color_jitter(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
     if not only or "bbox_aug" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_bbox_aug(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
