@@ -933,6 +933,40 @@ int detops_eval_proposal_overlaps(const float* dt_boxes, const float* gt_boxes, 
                                   detops_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cityscapes evaluation (csrc/cityscapes_eval.hip; reference data/datasets/evaluation/cityscapes/eval_instances.py,
+ * matchGtWithPred / prepareGtImage / preparePredImage).  For every instance and for every (ground truth, prediction) pair
+ * whose boxes overlap the reference crops full-size planes to a window, multiplies, sums and calls .item(): one host round
+ * trip each.  Here all the counts of one image are one call.  tests/golden/cityscapes_reference.npz holds what the
+ * reference's functions returned.
+ *
+ *   dt_planes [D, H, W], gt_planes [G, H, W] bytes: a NON-ZERO byte is a set pixel (bool, 0/1 and 0/255 planes all serve).
+ *   dt_box [D, 4], gt_box [G, 4] int32 (xmin, ymin, xmax, ymax): the reference's bbox.long() of the xyxy boxes.
+ *   The window of a box: rows [ymin, ymax) and columns [xmin, xmax), THE MAXIMA EXCLUSIVE (the reference's slices: the last
+ *     row and column of a tight box are left out, for ground truth and predictions alike), clamped to [0, H] x [0, W]
+ *     (the reference lets a negative minimum wrap around as a Python index; this library's choice); empty when a maximum does
+ *     not exceed its minimum.
+ *   dt_count [D], gt_count [G] int32: the set pixels of the instance's plane inside the window of its own box (pixelCount).
+ *   A pair (d, g) takes part iff isOverlapping: dt.xmin < gt.xmax && gt.xmin < dt.xmax && dt.ymin < gt.ymax &&
+ *     gt.ymin < dt.ymax on the boxes as given (not clamped).  Then
+ *       pair_box [d, g]  = (min(xmax) - max(xmin)) * (min(ymax) - max(ymin)) (boxIntersection; positive for boxes whose
+ *                          minima lie below their maxima; formed in 64 bits and saturated to the int32 range),
+ *       pair_mask [d, g] = the pixels set in BOTH planes inside the window of the UNION box (min of the minima, max of the
+ *                          maxima), again exclusive and clamped (maskIntersection).
+ *     Both are 0 for a pair that does not take part, and such a pair reads no plane.  pair_box, pair_mask [D, G] int32.
+ *   Every output element is written for every input, whatever the memory held before: the entry point's first launch
+ *   writes zeros and pair_box, the second adds the strips of every window with 32-bit integer atomics.  Integers only, so
+ *   two runs give identical bits.  Plane offsets are 64-bit (D * H * W may pass 2^31).  No workspace.
+ * DETOPS_EINVAL: D, G, H or W negative; H * W >= 2^31; D + G + D * G >= DETOPS_WINDOW_COUNTS_MAX_ITEMS (a work item is a
+ *   workgroup column of the grid); a null dt_box / dt_count with D > 0, gt_box / gt_count with G > 0, pair_box / pair_mask
+ *   with D * G > 0, dt_planes with D * H * W > 0 or gt_planes with G * H * W > 0.
+ * D == 0 or G == 0 still fills the other side's counts; H * W == 0 gives zero counts (pair_box is still formed).
+ * ---------------------------------------------------------------------------------------- */
+#define DETOPS_WINDOW_COUNTS_MAX_ITEMS 16777216
+int detops_window_counts(const unsigned char* dt_planes, const int32_t* dt_box, int D, const unsigned char* gt_planes,
+                         const int32_t* gt_box, int G, int H, int W, int32_t* dt_count, int32_t* gt_count, int32_t* pair_box,
+                         int32_t* pair_mask, detops_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Batch image preparation (csrc/image_prep.hip; extension: the reference resizes every image on the CPU with
  * torchvision over Pillow, data/transforms/transforms.py, and copies the padded fp32 batch to the device).  One launch
  * takes the raw RGB uint8 HWC images of a batch to the zero-padded fp32 batch tensor: Resize, RandomHorizontalFlip,

@@ -1522,6 +1522,43 @@ def eval_proposal_overlaps(dt_boxes, gt_boxes, dt_offset, gt_offset, gt_valid, l
     return out
 
 
+WINDOW_COUNTS_MAX_ITEMS = _lib._abi.WINDOW_COUNTS_MAX_ITEMS      # DETOPS_WINDOW_COUNTS_MAX_ITEMS: D + G + D * G stays below it
+
+
+def window_counts(dt_planes, dt_box, gt_planes, gt_box):
+    """The counts behind the Cityscapes AP of ONE image in one call (include/detops.h: detops_window_counts).
+    dt_planes [D, H, W], gt_planes [G, H, W] bool / uint8 (a non-zero byte is a set pixel); dt_box [D, 4], gt_box [G, 4]
+    int32 (xmin, ymin, xmax, ymax), the maxima exclusive -> (dt_count [D], gt_count [G], pair_box [D, G], pair_mask [D, G]),
+    all int32: the planes' set pixels inside their own boxes, and for every pair whose boxes overlap the box intersection
+    and the pixels set in both planes inside the union box; 0 for the other pairs.  Windows are clamped to the image.
+    Device tensors go to the kernel; CPU tensors take the numpy form of the same definition (_eval_cpu.window_counts)."""
+    if dt_planes.dim() != 3 or gt_planes.dim() != 3 or tuple(dt_planes.shape[1:]) != tuple(gt_planes.shape[1:]):
+        raise ValueError("window_counts: expected planes [D, H, W] and [G, H, W] of one image, got %s and %s"
+                         % (tuple(dt_planes.shape), tuple(gt_planes.shape)))
+    dt_planes, gt_planes = _u8("window_counts", dt_planes), _u8("window_counts", gt_planes)
+    (D, H, W), G = dt_planes.shape, gt_planes.shape[0]
+    if dt_box.dtype != torch.int32 or gt_box.dtype != torch.int32 or tuple(dt_box.shape) != (D, 4) or tuple(gt_box.shape) != (G, 4):
+        raise ValueError("window_counts: expected int32 boxes [%d, 4] and [%d, 4], got %s %s and %s %s"
+                         % (D, G, dt_box.dtype, tuple(dt_box.shape), gt_box.dtype, tuple(gt_box.shape)))
+    if H * W >= 2 ** 31 or D + G + D * G >= WINDOW_COUNTS_MAX_ITEMS:
+        raise ValueError("window_counts: H * W = %d must stay below 2^31 and D + G + D * G = %d below %d"
+                         % (H * W, D + G + D * G, WINDOW_COUNTS_MAX_ITEMS))
+    dt_box, gt_box = dt_box.contiguous(), gt_box.contiguous()
+    tensors = (dt_planes, dt_box, gt_planes, gt_box)
+    dev = dt_planes.device
+    if not any(on_device(t) for t in tensors):
+        out = _eval_cpu.window_counts(_np(dt_planes), _np(dt_box), _np(gt_planes), _np(gt_box))
+        return tuple(torch.from_numpy(o) for o in out)
+    _need_cuda("window_counts", *tensors)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = (torch.empty((D,), **i32), torch.empty((G,), **i32), torch.empty((D, G), **i32), torch.empty((D, G), **i32))
+    if D + G:
+        with _on_device(dt_planes), _timed(("window_counts[D=%d,G=%d,H=%d,W=%d]", (D, G, H, W)), out[0]):
+            check(lib.detops_window_counts(ptr(dt_planes), ptr(dt_box), D, ptr(gt_planes), ptr(gt_box), G, H, W,
+                                           *(ptr(o) for o in out), stream_of(dt_planes)), "window_counts")
+    return out
+
+
 def match_labels(matched, gt_labels=None, valid=None, dtype=torch.int64):
     """Matcher output [N,K] -> labels in one launch (extension; reference modeling/rpn/loss.py:70-88,
     roi_heads/box_head/loss.py:56-72): matched >= 0 -> gt_labels[n, matched] (1 when gt_labels is None), -1 -> 0,

@@ -20,6 +20,7 @@ RLE_STATUS = {1: "DETOPS_RLE_BAD_BYTE (a byte outside 48..111)", 2: "DETOPS_RLE_
 MASK_PACK_RLE_MAX_H = 4096  # DETOPS_MASK_PACK_RLE_MAX_H
 EVAL_OKS_MAX_K = 32  # DETOPS_EVAL_OKS_MAX_K
 EVAL_PROPOSALS_MAX_DT, EVAL_PROPOSALS_MAX_GT = 2048, 1024  # DETOPS_EVAL_PROPOSALS_MAX_DT / _MAX_GT
+WINDOW_COUNTS_MAX_ITEMS = 1 << 24  # DETOPS_WINDOW_COUNTS_MAX_ITEMS
 
 # the fields of struct DetopsTuning (csrc/detops_common.h) = the keys of detops_tuning_set / detops_tuning_get
 TUNING_KEYS = ("roi_bwd_impl", "roi_bwd_seg", "nms_fault", "nms_spin_budget", "roi_bwd_ring", "roi_bwd_ct", "roi_bwd_split",
@@ -103,6 +104,7 @@ SIGNATURES = {
                           + [c_int, _P, c_int] + [_P] * 5),
     "detops_eval_oks": (c_int, [_P] * 5 + [c_int] + [_P] * 3 + [c_int, ctypes.c_int64, ctypes.c_int64, _P, _P, _P]),
     "detops_eval_proposal_overlaps": (c_int, [_P] * 6 + [c_int] * 3 + [ctypes.c_int64] * 2 + [c_int, c_int, _P, _P]),
+    "detops_window_counts": (c_int, [_P, _P, c_int, _P, _P] + [c_int] * 3 + [_P] * 5),
     "detops_roi_align_fpn_forward_nhwc_workspace_bytes": (c_size_t, [c_int]),
     "detops_roi_align_fpn_forward_nhwc_f32": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P] + [c_int] * 8 + [c_float] * 3 + [_P, c_size_t, _P]),
     "detops_roi_align_fpn_backward_ring_nhwc_f32": (c_int, [_P] * 7 + [c_int] * 8 + [_P, c_size_t, _P]),

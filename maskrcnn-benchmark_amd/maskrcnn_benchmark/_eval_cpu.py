@@ -315,3 +315,35 @@ def eval_proposal_overlaps(dt_boxes, gt_boxes, dt_offset, gt_offset, gt_valid, l
                     overlaps[box_ind, :] = -1
                     overlaps[:, gt_ind] = -1
     return out
+
+
+# ------------------------------------------------------------------------------------------------ Cityscapes
+def _window(box, H, W):
+    """(xmin, ymin, xmax, ymax) -> the slices of rows [ymin, ymax) and columns [xmin, xmax) clamped to the image"""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    clamp = lambda v, hi: min(max(v, 0), hi)  # noqa: E731
+    return slice(clamp(y0, H), max(clamp(y1, H), clamp(y0, H))), slice(clamp(x0, W), max(clamp(x1, W), clamp(x0, W)))
+
+
+def window_counts(dt_planes, dt_box, gt_planes, gt_box):
+    """include/detops.h, "Cityscapes evaluation": planes [D, H, W] / [G, H, W] (non-zero = set), int boxes [D, 4] / [G, 4]
+    (xmin, ymin, xmax, ymax; maxima exclusive) -> (dt_count [D], gt_count [G], pair_box [D, G], pair_mask [D, G]) int32.  The
+    reference's loop (eval_instances.py: matchGtWithPred) with numpy sums in the place of its torch sums and .item()."""
+    dt_planes, gt_planes = np.asarray(dt_planes) != 0, np.asarray(gt_planes) != 0
+    dt_box, gt_box = np.asarray(dt_box, np.int64).reshape(-1, 4), np.asarray(gt_box, np.int64).reshape(-1, 4)
+    D, G = dt_planes.shape[0], gt_planes.shape[0]
+    H, W = dt_planes.shape[1:] if D else gt_planes.shape[1:]
+    dt_count = np.array([np.count_nonzero(dt_planes[d][_window(dt_box[d], H, W)]) for d in range(D)], np.int32).reshape(D)
+    gt_count = np.array([np.count_nonzero(gt_planes[g][_window(gt_box[g], H, W)]) for g in range(G)], np.int32).reshape(G)
+    pair_box, pair_mask = np.zeros((D, G), np.int32), np.zeros((D, G), np.int32)
+    lo = np.maximum(dt_box[:, None, :2], gt_box[None, :, :2])
+    hi = np.minimum(dt_box[:, None, 2:], gt_box[None, :, 2:])
+    # isOverlapping: strict on all four sides, each box's minimum against the OTHER box's maximum
+    overlapping = ((dt_box[:, None, :2] < gt_box[None, :, 2:]) & (gt_box[None, :, :2] < dt_box[:, None, 2:])).all(axis=2)
+    for d, g in zip(*np.nonzero(overlapping)):
+        inter = int(hi[d, g, 0] - lo[d, g, 0]) * int(hi[d, g, 1] - lo[d, g, 1])
+        pair_box[d, g] = min(max(inter, -2 ** 31), 2 ** 31 - 1)
+        union = np.concatenate([np.minimum(dt_box[d, :2], gt_box[g, :2]), np.maximum(dt_box[d, 2:], gt_box[g, 2:])])
+        win = _window(union, H, W)
+        pair_mask[d, g] = np.count_nonzero(dt_planes[d][win] & gt_planes[g][win])
+    return dt_count, gt_count, pair_box, pair_mask

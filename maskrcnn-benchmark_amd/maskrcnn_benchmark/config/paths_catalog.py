@@ -24,6 +24,13 @@ class DatasetCatalog(object):
                                       "ann_file": "coco/annotations/person_keypoints_train2017.json"},
         "keypoints_coco_2017_val": {"img_dir": "coco/val2017", "ann_file": "coco/annotations/person_keypoints_val2017.json"},
     }
+    # Cityscapes as the reference reads it (data/datasets/cityscapes.py): leftImg8bit/<split>/<city>/*_leftImg8bit.png and
+    # gtFine/<split>/<city>/*_polygons.json ("poly") or *_instanceIds.png ("mask"); minival: ten images of val
+    CITYSCAPES = {
+        "cityscapes_%s_instance_%s" % (mode, name): dict(
+            {"img_dir": "cityscapes/leftImg8bit", "ann_dir": "cityscapes/gtFine", "split": split, "mode": mode},
+            **({"mini": 10} if name == "minival" else {}))
+        for mode in ("poly", "mask") for name, split in (("train", "train"), ("val", "val"), ("minival", "val"))}
     REGISTERED = {}
 
     @staticmethod
@@ -35,7 +42,8 @@ class DatasetCatalog(object):
 
     @staticmethod
     def get(name):
-        """-> {"factory": "COCODataset", "args": {"root", "ann_file"}}"""
+        """-> {"factory": "COCODataset", "args": {"root", "ann_file"}}, or for the cityscapes_{poly,mask}_instance_* names
+        {"factory": "CityScapesDataset", "args": {"img_dir", "ann_dir", "split", "mode"[, "mini"]}}"""
         if name in DatasetCatalog.REGISTERED:
             return dict(factory="COCODataset", args=dict(DatasetCatalog.REGISTERED[name]))
         if name in DatasetCatalog.DATASETS:
@@ -43,4 +51,9 @@ class DatasetCatalog(object):
             data_dir = DatasetCatalog.DATA_DIR
             return dict(factory="COCODataset", args=dict(root=os.path.join(data_dir, attrs["img_dir"]),
                                                          ann_file=os.path.join(data_dir, attrs["ann_file"])))
+        if name in DatasetCatalog.CITYSCAPES:
+            attrs = dict(DatasetCatalog.CITYSCAPES[name])
+            attrs["img_dir"] = os.path.join(DatasetCatalog.DATA_DIR, attrs["img_dir"])
+            attrs["ann_dir"] = os.path.join(DatasetCatalog.DATA_DIR, attrs["ann_dir"])
+            return dict(factory="CityScapesDataset", args=attrs)
         raise RuntimeError("Dataset not available: {}".format(name))

@@ -1,5 +1,6 @@
 """make_data_loader (reference data/build.py).  Dataset names that start with `synthetic_` (and an empty list) go to the
-synthetic generator of data/synthetic.py unchanged; every other name is looked up in the catalog and read as COCO json.
+synthetic generator of data/synthetic.py unchanged; every other name is looked up in the catalog and read as COCO json,
+or, for the cityscapes_{poly,mask}_instance_* names, by data/datasets/cityscapes.py.
 
 The real-data loader: an aspect-ratio GroupedBatchSampler under DATALOADER.ASPECT_RATIO_GROUPING, an
 IterationBasedBatchSampler of MAX_ITER batches for training, torch's DistributedSampler when distributed, and the

@@ -1,1 +1,2 @@
 from .coco import COCODataset  # noqa: F401
+from .cityscapes import CityScapesDataset  # noqa: F401

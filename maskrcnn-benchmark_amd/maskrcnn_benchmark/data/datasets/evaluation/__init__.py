@@ -9,8 +9,12 @@ The average recall of RPN proposals (`box_only`) has names of its own too (box_p
 evaluate_box_proposals, do_box_proposal_evaluation; `inference(box_only=True)`); `evaluate`, `coco_evaluation` and
 `check_scope` still refuse `box_only`.
 
-Not built, and raising NotImplementedError: `box_only` and the `keypoints` IoU type through the generic entry points, and
-the Cityscapes evaluator.
+The Cityscapes instance-level AP has names of its own as well (cityscapes.py: CityscapesEvaluator, do_cityscapes_evaluation,
+finish_cityscapes; `inference()` routes a dataset whose `evaluation_style` is "cityscapes" there); `evaluate` still refuses
+that style.
+
+Not built, and raising NotImplementedError: `box_only`, the `keypoints` IoU type and the "cityscapes" style through the
+generic entry points.
 """
 import logging
 import os
@@ -20,6 +24,7 @@ import torch
 
 from .box_proposals import (BoxProposalEvaluator, do_box_proposal_evaluation, evaluate_box_proposals,  # noqa: F401
                             finish_box_proposals)
+from .cityscapes import CityscapesEvaluator, do_cityscapes_evaluation, finish_cityscapes  # noqa: F401
 from .coco_style import STAT_NAMES, STAT_ROWS, COCOStyleEvaluator, _feed, _num_classes  # noqa: F401
 from .keypoint_oks import KeypointOKSEvaluator, evaluate_keypoint_file, load_keypoint_results  # noqa: F401
 from .voc import do_voc_evaluation, eval_detection_voc  # noqa: F401
@@ -45,7 +50,8 @@ def evaluate(dataset, predictions, output_folder, **kwargs):
     if style == "voc":
         return voc_evaluation(**args)
     if style == "cityscapes":
-        raise NotImplementedError("the Cityscapes evaluator is not built")
+        raise NotImplementedError("the Cityscapes evaluation is not served by the generic entry points: it runs through "
+                                  "inference(), CityscapesEvaluator and do_cityscapes_evaluation")
     raise NotImplementedError("Unsupported dataset type {}.".format(dataset.__class__.__name__))
 
 

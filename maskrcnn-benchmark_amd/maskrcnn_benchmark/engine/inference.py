@@ -4,7 +4,9 @@ where they were made and only the match records are kept (data/datasets/evaluati
 detections themselves are written as COCO result files (data/datasets/evaluation/coco_results.py: bbox.json, segm.json,
 keypoints.json), batch by batch next to the evaluator; `evaluate=False` writes them and matches nothing.  Keypoints are
 scored on request (`keypoint_oks=True`: data/datasets/evaluation/keypoint_oks.py).  The proposals of an RPN-only model
-are scored by their average recall (`box_only=True`: data/datasets/evaluation/box_proposals.py).  Single process only.
+are scored by their average recall (`box_only=True`: data/datasets/evaluation/box_proposals.py).  A dataset whose
+`evaluation_style` is "cityscapes" feeds the Cityscapes evaluator the same way (data/datasets/evaluation/cityscapes.py).
+Single process only.
 Datasets that are not COCO-shaped keep the reference's flow: the predictions are collected and handed to `evaluate`."""
 import logging
 import os
@@ -12,8 +14,9 @@ import time
 
 import torch
 
-from maskrcnn_benchmark.data.datasets.evaluation import (BoxProposalEvaluator, COCOStyleEvaluator, check_scope, dataset_style,
-                                                         finish_box_proposals, finish_coco)
+from maskrcnn_benchmark.data.datasets.evaluation import (BoxProposalEvaluator, CityscapesEvaluator, COCOStyleEvaluator,
+                                                         check_scope, dataset_style, finish_box_proposals, finish_cityscapes,
+                                                         finish_coco)
 from maskrcnn_benchmark.data.datasets.evaluation import evaluate as evaluate_predictions
 from maskrcnn_benchmark.data.datasets.evaluation.coco_results import COCOResultsWriter
 from maskrcnn_benchmark.data.datasets.evaluation.coco_style import _num_classes
@@ -54,13 +57,19 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     dataset the loop feeds a BoxProposalEvaluator instead of the evaluator of `iou_types`, and the returned COCOResults has the
     one row `box_proposal` (AR@100 ... ARl@1000), saved as box_proposals.pth / box_proposals.txt; no result files are written
     for proposals.  Not together with keypoint_oks, evaluate=False or box augmentation.  ValueError: the model's output has
-    no `objectness`, i.e. the model is not RPN-only."""
+    no `objectness`, i.e. the model is not RPN-only.
+    A dataset whose `evaluation_style` is "cityscapes" (data/datasets/cityscapes.py): the loop feeds a CityscapesEvaluator with
+    the dataset's CLASSES and `iou_types` ("bbox", "segm"), and the result is its summarize(): {iou type: {"averages": the
+    reference's avgDict, "ap": [1, classes, 10]}}; with an output folder evaluationResults/boxResult.json / maskResult.json
+    are written, no COCO result files.  Refused for such a dataset: keypoint_oks, box_only, evaluate=False, and box
+    augmentation together with "segm" (the mask head is not run under it)."""
     if not evaluate and not output_folder:
         raise ValueError("inference(evaluate=False) writes result files only: it needs output_folder=")
     if get_world_size() > 1:
         raise NotImplementedError("evaluation is single-process only: run tools/test_net.py without a distributed launcher "
                                   "(world size %d)" % get_world_size())
     logger = logging.getLogger("maskrcnn_benchmark.inference")
+    requested_iou_types = tuple(iou_types)
     built_with = _built_with(model)
     built_aug = None if built_with is None else bool(built_with.TEST.BBOX_AUG.ENABLED)
     if bbox_aug is None:
@@ -83,8 +92,16 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     device = torch.device(device)
     dataset = data_loader.dataset
     logger.info("Start evaluation on {} dataset({} images).".format(dataset_name, len(dataset)))
-    streaming = dataset_style(dataset) == "coco"
+    cityscapes = dataset_style(dataset) == "cityscapes"
+    streaming = dataset_style(dataset) == "coco" or cityscapes
     evaluators, writer = [], None
+    if cityscapes:
+        if keypoint_oks or box_only or not evaluate:
+            raise NotImplementedError("inference() on a Cityscapes dataset scores bbox and segm AP only: not keypoint_oks, "
+                                      "box_only or evaluate=False")
+        if bbox_aug and "segm" in requested_iou_types:
+            raise NotImplementedError("inference() on a Cityscapes dataset: segm is not scored under box augmentation (the "
+                                      "mask head is not run); ask for iou_types=('bbox',)")
     if keypoint_oks and (not streaming or box_only or bbox_aug):
         raise NotImplementedError("inference(keypoint_oks=True): keypoints are scored for COCO-shaped datasets and detections "
                                   "only (not box_only proposals, not under box augmentation)")
@@ -93,14 +110,16 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
                                   "only (not box_only proposals)")
     if box_only and bbox_aug:
         raise NotImplementedError("inference(box_only=True): proposals are not scored under box augmentation")
-    if streaming and evaluate and box_only:
+    if cityscapes:
+        evaluators = [CityscapesEvaluator(dataset.CLASSES, iou_types)]
+    elif streaming and evaluate and box_only:
         evaluators = [BoxProposalEvaluator()]
     elif streaming and evaluate:
         check_scope(False, iou_types)
         evaluators = [COCOStyleEvaluator(iou_types, _num_classes(dataset, 81))]
         if keypoint_oks:
             evaluators.append(KeypointOKSEvaluator(_num_classes(dataset, 2)))
-    if streaming and output_folder and not box_only:
+    if streaming and output_folder and not box_only and not cityscapes:
         writer = COCOResultsWriter(dataset, tuple(iou_types) + (("keypoints",) if keypoint_oks and "keypoints" not in iou_types else ()))
     model.eval()
     predictions = {}
@@ -144,6 +163,8 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     if streaming:
         logger.info("Matched {} detections against {} ground truths of {} images".format(
             evaluators[0].num_detections, evaluators[0].num_groundtruths, evaluators[0].num_images))
+        if cityscapes:
+            return finish_cityscapes(evaluators[0], output_folder, expected_results, expected_results_sigma_tol)
         if box_only:
             return finish_box_proposals(evaluators[0], output_folder, expected_results, expected_results_sigma_tol)
         return finish_coco(evaluators, output_folder, expected_results, expected_results_sigma_tol)

@@ -1212,6 +1212,109 @@ def bench_proposal_recall(C, iters):
     return res
 
 
+def bench_cityscapes(C, iters):
+    """Cityscapes window counts (csrc/cityscapes_eval.hip): one image of 1024 x 2048, D = 100 pasted predictions and G = 30
+    ground truths whose planes fill ellipses in their boxes; boxes drawn like a street scene (many small, a few large), about
+    300 overlapping pairs.  Rows: the entry point alone on prebuilt device arrays; _C.window_counts through the wrapper (its
+    checks and four allocations included); the reference's own loop (eval_instances.py: matchGtWithPred) on the same device
+    tensors: crop, mul, sum and .item() per pair and per instance, which is the yardstick.  Every row is the MEDIAN of
+    `iters` samples (50 by default) after warm-up, each sample one call between two HIP events.  bytes = the window bytes the
+    entry point reads: every instance's own window once, and both planes of every overlapping pair's union window."""
+    from maskrcnn_benchmark import _eval_cpu, _lib
+    H, W, D, G = 1024, 2048, 100, 30
+    rng = np.random.RandomState(11)
+
+    def boxes(n, jitter_of=None):
+        side = np.exp(rng.uniform(np.log(16), np.log(90), n))
+        side[rng.rand(n) < 0.12] *= 5                                        # a few large ones
+        w, h = side * rng.uniform(0.5, 1.6, n), side * rng.uniform(0.8, 2.2, n)
+        cx, cy = rng.uniform(0, W, n), rng.uniform(0.35 * H, 0.8 * H, n)       # a band around the horizon
+        if jitter_of is not None:                                              # most predictions sit on a ground truth
+            k = rng.randint(0, len(jitter_of), n)
+            on = rng.rand(n) < 0.9
+            g = jitter_of[k]
+            cx, cy = np.where(on, (g[:, 0] + g[:, 2]) / 2 + rng.uniform(-8, 8, n), cx), np.where(on, (g[:, 1] + g[:, 3]) / 2 + rng.uniform(-8, 8, n), cy)
+            w, h = np.where(on, (g[:, 2] - g[:, 0]) * rng.uniform(0.8, 1.25, n), w), np.where(on, (g[:, 3] - g[:, 1]) * rng.uniform(0.8, 1.25, n), h)
+        b = np.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2], 1)
+        return np.clip(b, 0, [W, H, W, H]).astype(np.int32)
+
+    def ellipses(b):
+        ys, xs = torch.arange(H, device="cuda").view(1, H, 1), torch.arange(W, device="cuda").view(1, 1, W)
+        bt = _t(b).to(torch.float32)
+        cx, cy = ((bt[:, 0] + bt[:, 2]) / 2).view(-1, 1, 1), ((bt[:, 1] + bt[:, 3]) / 2).view(-1, 1, 1)
+        rx, ry = ((bt[:, 2] - bt[:, 0]) / 2).clamp(min=1).view(-1, 1, 1), ((bt[:, 3] - bt[:, 1]) / 2).clamp(min=1).view(-1, 1, 1)
+        return ((((xs - cx) / rx) ** 2 + ((ys - cy) / ry) ** 2) <= 1).to(torch.uint8).contiguous()
+
+    gt_box = boxes(G)
+    dt_box = boxes(D, gt_box)
+    dt_planes, gt_planes, dt_box_d, gt_box_d = ellipses(dt_box), ellipses(gt_box), _t(dt_box), _t(gt_box)
+
+    def area(b):
+        return np.maximum(b[..., 2] - b[..., 0], 0) * np.maximum(b[..., 3] - b[..., 1], 0)
+
+    over = ((dt_box[:, None, :2] < gt_box[None, :, 2:]) & (gt_box[None, :, :2] < dt_box[:, None, 2:])).all(axis=2)
+    union = np.concatenate([np.minimum(dt_box[:, None, :2], gt_box[None, :, :2]), np.maximum(dt_box[:, None, 2:], gt_box[None, :, 2:])], axis=2)
+    alg = int(area(dt_box).sum() + area(gt_box).sum() + 2 * (area(union) * over).sum())
+
+    def median_us(fn, warmup=5):
+        for _ in range(warmup):
+            fn()
+        samples = []
+        for _ in range(iters):
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            fn()
+            end.record()
+            torch.cuda.synchronize()
+            samples.append(start.elapsed_time(end) * 1000.0)
+        return float(np.median(samples))
+
+    i32 = dict(dtype=torch.int32, device="cuda")
+    outs = (torch.empty((D,), **i32), torch.empty((G,), **i32), torch.empty((D, G), **i32), torch.empty((D, G), **i32))
+    raw = lambda: _lib.check(_lib.lib.detops_window_counts(  # noqa: E731
+        dt_planes.data_ptr(), dt_box_d.data_ptr(), D, gt_planes.data_ptr(), gt_box_d.data_ptr(), G, H, W,
+        *(o.data_ptr() for o in outs), _lib.stream_of(outs[0])), "window_counts")
+    name = "1024 x 2048, D=100, G=30, %d overlapping pairs" % int(over.sum())
+    res = [_entry("detops_window_counts entry point, " + name, median_us(raw), alg)]
+    # where the time goes: the same grid with empty windows (xmax = xmin: every workgroup leaves after reading its boxes,
+    # no plane is read), and one instance (the floor of the entry point's two launches)
+    flat_d, flat_g = dt_box_d.clone(), gt_box_d.clone()
+    flat_d[:, 2], flat_g[:, 2] = flat_d[:, 0], flat_g[:, 0]
+    empty = lambda: _lib.check(_lib.lib.detops_window_counts(  # noqa: E731
+        dt_planes.data_ptr(), flat_d.data_ptr(), D, gt_planes.data_ptr(), flat_g.data_ptr(), G, H, W,
+        *(o.data_ptr() for o in outs), _lib.stream_of(outs[0])), "window_counts")
+    res.append(_entry("  the same grid, every window empty (no plane read)", median_us(empty), 0))
+    one = lambda: _lib.check(_lib.lib.detops_window_counts(  # noqa: E731
+        dt_planes.data_ptr(), dt_box_d.data_ptr(), 1, gt_planes.data_ptr(), gt_box_d.data_ptr(), 0, H, W,
+        *(o.data_ptr() for o in outs), _lib.stream_of(outs[0])), "window_counts")
+    res.append(_entry("  one instance, no pair (two launches)", median_us(one), int(area(dt_box[:1]).sum())))
+    wrapped = lambda: C.window_counts(dt_planes, dt_box_d, gt_planes, gt_box_d)  # noqa: E731
+    res.append(_entry("_C.window_counts through the wrapper, same image", median_us(wrapped), alg))
+    ref = _eval_cpu.window_counts(dt_planes.cpu().numpy(), dt_box, gt_planes.cpu().numpy(), gt_box)
+    res[-1].update({"equal_to_numpy": bool(all(np.array_equal(a.cpu().numpy(), b) for a, b in zip(wrapped(), ref))),
+                    "overlapping_pairs": int(over.sum())})
+    dt_l, gt_l = dt_box.tolist(), gt_box.tolist()
+
+    def reference_loop():
+        dt_count = [dt_planes[d][b[1]:b[3], b[0]:b[2]].sum().item() for d, b in enumerate(dt_l)]
+        gt_count = [gt_planes[g][b[1]:b[3], b[0]:b[2]].sum().item() for g, b in enumerate(gt_l)]
+        pair_mask = np.zeros((D, G), np.int64)
+        for g, a in enumerate(gt_l):
+            for d, b in enumerate(dt_l):
+                if not (a[0] < b[2] and b[0] < a[2] and a[1] < b[3] and b[1] < a[3]):
+                    continue
+                x0, y0, x1, y1 = min(a[0], b[0]), min(a[1], b[1]), max(a[2], b[2]), max(a[3], b[3])
+                pair_mask[d, g] = torch.sum(torch.mul(gt_planes[g][y0:y1, x0:x1], dt_planes[d][y0:y1, x0:x1])).item()
+        return dt_count, gt_count, pair_mask
+
+    us = median_us(reference_loop, warmup=2)
+    dc, gc, pm = reference_loop()
+    res.append(_entry("torch: the reference's loop (crop, mul, sum, .item()) on the same device tensors", us, alg,
+                      {"equal_to_numpy": bool(np.array_equal(dc, ref[0]) and np.array_equal(gc, ref[1]) and np.array_equal(pm, ref[3])),
+                       "ratio_to_entry_point": round(us / res[0]["us"], 1)}))
+    return res
+
+
 def copy_ceiling(iters):
     a = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
     b = torch.empty_like(a)
@@ -1281,6 +1384,8 @@ def main():
         res += bench_keypoint_oks(C, args.iters)
     if not only or "proposal_recall" in only:
         res += bench_proposal_recall(C, args.iters)
+    if not only or "cityscapes" in only:
+        res += bench_cityscapes(C, args.iters)
     if not only or "coco_results" in only:
         copy_rows = [r for r in res if r["op"].startswith("hbm copy")]
         res += bench_coco_results(C, args.iters, copy_rows[0]["gbs"] if copy_rows else None)
